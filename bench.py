@@ -22,6 +22,14 @@ roofline, CPU restatement baseline).
 --dry-run exercises the launch + gather path on the CPU (gloo, synthetic
 outputs, no solve) for the multi-process tests.
 
+A plain run sets up, warms up, times the --steps steps and prints the result
+line (the headline rate, `ms_per_step`, the configuration and the pipeline's
+HBM roofline from the same timed steps). --full adds everything that takes
+runs of its own: per-kernel times, the decision-margin A/B run and its swarm
+statistics, the collision-avoidance probe and the CPU baseline with its
+parity check. --dump-outputs DIR writes what the last timed step computed
+(rank 0's shard) as DIR/<name>.npy; same arguments, same inputs, run to run.
+
 Prints ONE JSON line on rank 0 (the driver's contract).
 """
 import argparse
@@ -124,6 +132,50 @@ def committed_profile(prefix, n, B, kernel):
         if c.get("n") == n and c.get("B_per_gpu") == B and kernel in d.get("kernels", {}):
             return d["kernels"][kernel], os.path.relpath(f, ROOT)
     return None, None
+
+
+DUMP_BUDGET = 48 << 20  # bytes --dump-outputs writes at most (a seeded sample of rows above it)
+
+
+def dump_outputs(dirname, tensors, seed):
+    """--dump-outputs: write `tensors` (name -> tensor; a shared leading axis
+    of swarms / formations) as dirname/<name>.npy. Floating-point arrays keep
+    their type, 8- and 16-bit integers go to float32 and wider ones to
+    float64 (both exact); the 16-byte status records are written field by
+    field (status_flags, ..., status_margin). When all rows would exceed
+    DUMP_BUDGET, a fixed sample of them is kept -- sorted, drawn without
+    replacement from RandomState(seed) -- and sample_rows.npy names them."""
+    import numpy as np
+    import torch
+    from aclswarm_amd import _lib as L
+
+    def out_dtype(t):
+        if t.dtype.is_floating_point:
+            return np.float32 if t.dtype == torch.float32 else np.float64
+        return np.float32 if t.element_size() <= 2 else np.float64
+
+    B = next(iter(tensors.values())).shape[0]
+    row_bytes = 8  # sample_rows
+    for name, t in tensors.items():
+        row_bytes += (8 * len(L.STATUS_DTYPE.names) if name == "status" else
+                      np.dtype(out_dtype(t)).itemsize * (t[0].numel() if B else 0))
+    S = max(1, min(B, DUMP_BUDGET // row_bytes))
+    rows = (np.arange(B) if S >= B else
+            np.sort(np.random.RandomState(seed).choice(B, S, replace=False)))
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "sample_rows.npy"), rows.astype(np.float64))
+    for name, t in tensors.items():
+        if S < B:
+            t = t[torch.from_numpy(rows).to(t.device)]
+        a = t.detach().cpu().numpy()
+        if name == "status":
+            rec = np.ascontiguousarray(a).view(L.STATUS_DTYPE).reshape(-1)
+            for f in L.STATUS_DTYPE.names:
+                dt = np.float32 if rec[f].dtype.itemsize <= 2 or rec[f].dtype.kind == "f" \
+                    else np.float64
+                np.save(os.path.join(dirname, f"status_{f}.npy"), rec[f].astype(dt))
+        else:
+            np.save(os.path.join(dirname, name + ".npy"), a.astype(out_dtype(t)))
 
 
 def cpu_baseline(w, out, budget_s, nthreads):
@@ -262,14 +314,17 @@ def bench_c5(args, world, rank, local):
     adj = adjb.to(torch.float64)
     torch.cuda.synchronize()
     lib = L.lib()
-    # GEMM flops of one batch, counted on the device in an untimed pass
-    counter = torch.zeros(1, dtype=torch.int64, device=dev)
-    lib.acl_internal_admm_flop_counter(ctypes.c_void_p(counter.data_ptr()))
-    G, its = engine.admm_design(pts, adj)
-    torch.cuda.synchronize()
-    lib.acl_internal_admm_flop_counter(ctypes.c_void_p(0))
-    flops = float(counter.item())
-    for _ in range(max(0, args.warmup - 1)):
+    flops = None
+    if args.full:
+        # GEMM flops of one batch, counted on the device in an untimed pass
+        # (it stands for the first warmup step)
+        counter = torch.zeros(1, dtype=torch.int64, device=dev)
+        lib.acl_internal_admm_flop_counter(ctypes.c_void_p(counter.data_ptr()))
+        G, its = engine.admm_design(pts, adj)
+        torch.cuda.synchronize()
+        lib.acl_internal_admm_flop_counter(ctypes.c_void_p(0))
+        flops = float(counter.item())
+    for _ in range(max(0, args.warmup - 1) if args.full else args.warmup):
         G, its = engine.admm_design(pts, adj)
     torch.cuda.synchronize()
     if world > 1:
@@ -293,8 +348,8 @@ def bench_c5(args, world, rank, local):
     if world > 1:
         dist.all_reduce(dt_t, op=dist.ReduceOp.MAX)
     dt_max = float(dt_t.item())
-    itn = its.cpu()
-    ach = flops / (batch_ms * 1e-3) / 1e12
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"gains": G, "iters": its}, args.seed)
     line = {
         "metric": METRIC_C5, "value": world * F / dt_max, "unit": "formations/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -306,20 +361,28 @@ def bench_c5(args, world, rank, local):
                                  f"np.random.seed(s), s = {rank * F}..{rank * F + F - 1} per rank",
                    "n": n, "F_per_gpu": F, "F_total": world * F,
                    "parallelism": f"formation-sharded x{world}"},
-        "roofline": {"bound": "mfma", "scope": "batch",
-                     "what": "the batch's fp64 GEMM flops (counted per tile on the device, "
-                             "symmetric products as upper-triangle tiles) / batch time",
-                     "achieved": ach, "peak": FP64_MATRIX_PEAK_TF, "unit": "TFLOP/s",
-                     "frac": ach / FP64_MATRIX_PEAK_TF, "traffic": None,
-                     "measured_instruction_peak": FP64_MFMA_MEASURED_TF,
-                     "frac_of_measured_peak": ach / FP64_MFMA_MEASURED_TF,
-                     "measured_peak_source": "profiles/r4_mfma_f64_peak.txt (scripts/mfma_f64_peak.hip)",
-                     "gemm_flops_per_batch": flops, "batch_ms_events": batch_ms},
-        "iters_xy": {int(k): int(v) for k, v in zip(*torch.unique(itn[:, 0], return_counts=True))},
-        "iters_z": {int(k): int(v) for k, v in zip(*torch.unique(itn[:, 1], return_counts=True))},
-        "finite": bool(torch.isfinite(G).all().item()),
     }
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full:
+        itn = its.cpu()
+        ach = flops / (batch_ms * 1e-3) / 1e12
+        line.update({
+            "roofline": {"bound": "mfma", "scope": "batch",
+                         "what": "the batch's fp64 GEMM flops (counted per tile on the device, "
+                                 "symmetric products as upper-triangle tiles) / batch time",
+                         "achieved": ach, "peak": FP64_MATRIX_PEAK_TF, "unit": "TFLOP/s",
+                         "frac": ach / FP64_MATRIX_PEAK_TF, "traffic": None,
+                         "measured_instruction_peak": FP64_MFMA_MEASURED_TF,
+                         "frac_of_measured_peak": ach / FP64_MFMA_MEASURED_TF,
+                         "measured_peak_source": "profiles/r4_mfma_f64_peak.txt "
+                                                 "(scripts/mfma_f64_peak.hip)",
+                         "gemm_flops_per_batch": flops, "batch_ms_events": batch_ms},
+            "iters_xy": {int(k): int(v)
+                         for k, v in zip(*torch.unique(itn[:, 0], return_counts=True))},
+            "iters_z": {int(k): int(v)
+                        for k, v in zip(*torch.unique(itn[:, 1], return_counts=True))},
+            "finite": bool(torch.isfinite(G).all().item()),
+        })
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         line["cpu_baseline"] = cpu_baseline_admm(pts, adj, G, its, args.cpu_budget)
     if rank == 0:
         print(json.dumps(line), flush=True)
@@ -358,6 +421,8 @@ def dry_run(args, world, rank):
     dt = torch.tensor([(time.perf_counter() - t0) / args.steps], dtype=torch.float64)
     if world > 1:
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"P_out": res[0], "status": res[1]}, args.seed)
     if rank == 0:
         print(json.dumps({
             "metric": METRIC, "value": world * B / float(dt.item()), "unit": "solves/s",
@@ -385,8 +450,16 @@ def main():
                     help="0: every swarm has its own formation; F>0: F shared formations")
     ap.add_argument("--full-rounds", action="store_true",
                     help="run all 2N CBAA rounds instead of stopping at the fixed point")
-    ap.add_argument("--cpu-budget", type=float, default=16.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: per-kernel times, "
+                         "the decision-margin A/B run and its swarm statistics, the collision-"
+                         "avoidance probe, the CPU baseline and its parity sample (c5: the flop-"
+                         "counting pass and MFMA roofline, iteration counts, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (rank 0's "
+                         "shard; a fixed seeded sample of its rows above 48 MiB) as DIR/<name>.npy")
+    ap.add_argument("--cpu-budget", type=float, default=16.0, help="with --full")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--gain-planes", type=int, default=5, choices=(5, 9),
                     help="5: ADMM-structured gain blocks (the reference's gains); "
@@ -403,10 +476,11 @@ def main():
                          "collision-list counters per call; A/B of ABI 10's persistent workspace)")
     ap.add_argument("--margin", action="store_true",
                     help="time the headline with the decision margin tracked (default: the "
-                         "reference's work only, acl_solve_args_t::skip_margin; the margin-on "
-                         "rate is measured beside it either way)")
+                         "reference's work only, acl_solve_args_t::skip_margin; with --full the "
+                         "other mode's rate is measured beside it either way)")
     ap.add_argument("--no-ca-probe", action="store_true",
-                    help="skip the crowded (collision-avoidance) probe reported beside the headline")
+                    help="with --full: skip the crowded (collision-avoidance) probe reported "
+                         "beside the headline")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU/gloo rehearsal of the launch + gather path (no GPU, no solve)")
     args = ap.parse_args()
@@ -545,13 +619,26 @@ def main():
     # skip_margin) unless --margin; then the other mode on the same swarms,
     # whose margin-on run gives the swarm statistics (fragile counts, min margin)
     # (the margin-on run last: its outputs stay in `out` for the CPU check)
+    # A plain run times the headline only; the other mode, the statistics and
+    # the per-launch kernel times are --full's.
+    full = args.full
+
+    def dump():  # the headline's last step, before any later run reuses `out`
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, out, args.seed)
+
+    dt_alt = res = None
     if args.margin:
-        dt_alt, _, _, _, _ = timed(False, False)
-        dt_max, call_ms, kms, kcnt, res = timed(True, True)
+        if full:
+            dt_alt, _, _, _, _ = timed(False, False)
+        dt_max, call_ms, kms, kcnt, res = timed(True, full)
+        dump()
     else:
-        dt_max, call_ms, kms, kcnt, _ = timed(False, True)
-        dt_alt, _, _, _, res = timed(True, False)
-    margin_line = {
+        dt_max, call_ms, kms, kcnt, _ = timed(False, full)
+        dump()
+        if full:
+            dt_alt, _, _, _, res = timed(True, False)
+    margin_line = None if not full else {
         "headline_tracks_margin": bool(args.margin),
         "value_margin_on": world * B / (dt_max if args.margin else dt_alt),
         "value_margin_off": world * B / (dt_alt if args.margin else dt_max),
@@ -561,7 +648,7 @@ def main():
                 "assignments, rounds and commands bit for bit (tests/test_gpu_fused.py::"
                 "test_skip_margin_same_outcome); `stats` comes from the margin-on run",
     }
-    stats = D.stats_dict(res[2], res[3])
+    stats = D.stats_dict(res[2], res[3]) if full else None
 
     # collision-avoidance probe: the same swarms crowded (positions scaled by
     # 0.3 about each swarm's centre, most vehicles inside the 1.5 m avoidance
@@ -569,7 +656,7 @@ def main():
     # (safety.cpp:412-541) runs for most vehicles; reported beside the
     # headline, which is the reference's spacing (start.sh discs, no CA)
     ca_probe = None
-    if not args.no_ca_probe:
+    if full and not args.no_ca_probe:
         qc = w["q"].clone()
         cen = qc[:, :, :2].mean(dim=1, keepdim=True)
         qc[:, :, :2] = cen + 0.3 * (qc[:, :, :2] - cen)
@@ -609,80 +696,82 @@ def main():
     # per-vehicle rows (none here).
     a_all, g_all, s_all, e_avg = algorithmic_bytes(w, 0, B)
     fused = w["planes"] == 5
-    mg = "true" if args.margin else "false"  # the timed kernels' margin template argument
-    if fused:
-        per_launch = {"auction": a_all + g_all, "gain": 0, "ca": s_all}
-        auction_sym = (f"acl_amd::auction_kernel<1, 128, true, false, {mg}>" if n <= 32 else
-                       f"acl_amd::auction_kernel<1, 256, true, false, {mg}>" if n <= 64 else
-                       f"acl_amd::auction_kernel<2, 512, true, false, {mg}>" if n <= 128 else
-                       f"acl_amd::solve_wide_kernel<true, false, {mg}>")
-        gain_sym = (f"acl_amd::gain_kernel<{w['planes']}, false, 256>" if n <= 128 else
-                    f"acl_amd::gain_kernel<{w['planes']}, false, 1024>")
-        align_sym = "acl_amd::align_kernel<2>" if n <= 128 else "acl_amd::align_wide_kernel"
-    else:
-        per_launch = {"auction": a_all, "gain": g_all, "ca": s_all}
-        auction_sym = ((f"acl_amd::auction_kernel<1, 128, false, false, {mg}>" if n <= 32 else
-                        f"acl_amd::auction_kernel<1, 256, false, false, {mg}>" if n <= 64 else
-                        f"acl_amd::auction_kernel<2, 512, false, false, {mg}>") if n <= 128
-                       else "acl_amd::solve_wide_kernel")
-        # n > 128: the control law is the directed walk on 1 024-thread workgroups
-        gain_sym = ("acl_amd::gain_pair_kernel<false, false>" if w["planes"] == 5 and n <= 128
-                    else f"acl_amd::gain_kernel<{w['planes']}, false, 1024>" if n > 128
-                    else f"acl_amd::gain_kernel<{w['planes']}, false, 256>")
-    kern = {}
-    for k, (name, sym) in enumerate((("auction", auction_sym), ("gain", gain_sym),
-                                     ("ca", "acl_amd::ca_pair_kernel" if n <= 128
-                                      else "acl_amd::ca_kernel"))):
-        avg = kms[k] / max(kcnt[k], 1)
-        ach = per_launch[name] / (avg * 1e-3) / 1e9
-        pm, src = (committed_profile("pmc_traffic", n, B, sym) if args.formations == 0
-                   else (None, None))
-        kern[name] = {"kernel": sym, "launches_per_step": 1, "avg_launch_ms": avg,
-                      "bytes_per_launch": per_launch[name], "achieved_GBs": ach,
-                      "frac": ach / HBM_PEAK_GBS,
-                      "traffic": pm["hbm_bytes"] if pm else None, "traffic_source": src}
-    if fused:
-        kern["auction"]["what"] = ("fused: CBAA, adoption, then DistCntrl + saturation + the "
-                                   "collision test in the same workgroup; for n > 64 the "
-                                   f"alignment runs as its own launch just before ({align_sym}), "
-                                   "timed with it")
-        kern["gain"]["what"] = "directed gain kernel for swarms with per-vehicle rows only"
-    # the auction kernel is bound by an issue port, not HBM: its utilisation
-    # from the committed SQ counters of the same configuration
-    # (scripts/gpu_pmc_auction.sh -> scripts/pmc_auction_summary.py).
-    # VALU: SQ_ACTIVE_INST_VALU x 4 / SIMD-cycles (fp64 VALU ops occupy a
-    # SIMD for several cycles, which instruction counts under-read);
-    # SALU and LDS: instructions per CU-cycle at one issue per cycle.
-    iss, isrc = committed_profile("pmc_auction", n, B, auction_sym)
-    if iss:
-        kern["auction"]["issue"] = dict(iss, source=isrc)
-        # the auction's own roofline: its busiest port as profiled (a ratio
-        # of the profiled run's counters to its own kernel time; this run's
-        # `avg_launch_ms` also spans the alignment launch)
-        scale = 1.0
-        ports = {}
-        if "valu_active" in iss:
-            ports["valu-active"] = iss["valu_active"] * scale
-        for p in ("salu", "lds"):
-            if p + "_issue_frac" in iss:
-                ports[p + "-issue"] = iss[p + "_issue_frac"] * scale
-        if ports:
-            top = max(ports, key=ports.get)
-            kern["auction"]["roofline"] = {"bound": top, "frac": ports[top],
-                                           "ports": ports, "source": isrc}
     pipe_bytes = a_all + g_all + s_all
     pipe_ach = pipe_bytes / (call_ms * 1e-3) / 1e9
-    tr = [kern[k]["traffic"] for k in (("auction",) if fused else ("auction", "gain"))]
-    if fused and n > 64:
-        # the alignment launch that precedes the fused one (its inputs and the
-        # workspace round trip of its results) is in the same timed window
-        am, _ = (committed_profile("pmc_traffic", n, B, align_sym)
-                 if args.formations == 0 else (None, None))
-        tr.append(am["hbm_bytes"] if am else None)
-        kern["auction"]["traffic_align_kernel"] = am["hbm_bytes"] if am else None
-    pipe_traffic = sum(tr) if all(x is not None for x in tr) else None
-    pipe_traffic_src = kern["auction"]["traffic_source"] if pipe_traffic is not None else None
-    gk = kern["auction" if fused else "gain"]
+    kern = pipe_traffic = pipe_traffic_src = gk = None
+    if full:  # per-launch kernel times (timed(.., ktimes=True)) and the committed counters
+        mg = "true" if args.margin else "false"  # the timed kernels' margin template argument
+        if fused:
+            per_launch = {"auction": a_all + g_all, "gain": 0, "ca": s_all}
+            auction_sym = (f"acl_amd::auction_kernel<1, 128, true, false, {mg}>" if n <= 32 else
+                           f"acl_amd::auction_kernel<1, 256, true, false, {mg}>" if n <= 64 else
+                           f"acl_amd::auction_kernel<2, 512, true, false, {mg}>" if n <= 128 else
+                           f"acl_amd::solve_wide_kernel<true, false, {mg}>")
+            gain_sym = (f"acl_amd::gain_kernel<{w['planes']}, false, 256>" if n <= 128 else
+                        f"acl_amd::gain_kernel<{w['planes']}, false, 1024>")
+            align_sym = "acl_amd::align_kernel<2>" if n <= 128 else "acl_amd::align_wide_kernel"
+        else:
+            per_launch = {"auction": a_all, "gain": g_all, "ca": s_all}
+            auction_sym = ((f"acl_amd::auction_kernel<1, 128, false, false, {mg}>" if n <= 32 else
+                            f"acl_amd::auction_kernel<1, 256, false, false, {mg}>" if n <= 64 else
+                            f"acl_amd::auction_kernel<2, 512, false, false, {mg}>") if n <= 128
+                           else "acl_amd::solve_wide_kernel")
+            # n > 128: the control law is the directed walk on 1 024-thread workgroups
+            gain_sym = ("acl_amd::gain_pair_kernel<false, false>" if w["planes"] == 5 and n <= 128
+                        else f"acl_amd::gain_kernel<{w['planes']}, false, 1024>" if n > 128
+                        else f"acl_amd::gain_kernel<{w['planes']}, false, 256>")
+        kern = {}
+        for k, (name, sym) in enumerate((("auction", auction_sym), ("gain", gain_sym),
+                                         ("ca", "acl_amd::ca_pair_kernel" if n <= 128
+                                          else "acl_amd::ca_kernel"))):
+            avg = kms[k] / max(kcnt[k], 1)
+            ach = per_launch[name] / (avg * 1e-3) / 1e9
+            pm, src = (committed_profile("pmc_traffic", n, B, sym) if args.formations == 0
+                       else (None, None))
+            kern[name] = {"kernel": sym, "launches_per_step": 1, "avg_launch_ms": avg,
+                          "bytes_per_launch": per_launch[name], "achieved_GBs": ach,
+                          "frac": ach / HBM_PEAK_GBS,
+                          "traffic": pm["hbm_bytes"] if pm else None, "traffic_source": src}
+        if fused:
+            kern["auction"]["what"] = ("fused: CBAA, adoption, then DistCntrl + saturation + the "
+                                       "collision test in the same workgroup; for n > 64 the "
+                                       "alignment runs as its own launch just before "
+                                       f"({align_sym}), timed with it")
+            kern["gain"]["what"] = "directed gain kernel for swarms with per-vehicle rows only"
+        # the auction kernel is bound by an issue port, not HBM: its utilisation
+        # from the committed SQ counters of the same configuration
+        # (scripts/gpu_pmc_auction.sh -> scripts/pmc_auction_summary.py).
+        # VALU: SQ_ACTIVE_INST_VALU x 4 / SIMD-cycles (fp64 VALU ops occupy a
+        # SIMD for several cycles, which instruction counts under-read);
+        # SALU and LDS: instructions per CU-cycle at one issue per cycle.
+        iss, isrc = committed_profile("pmc_auction", n, B, auction_sym)
+        if iss:
+            kern["auction"]["issue"] = dict(iss, source=isrc)
+            # the auction's own roofline: its busiest port as profiled (a ratio
+            # of the profiled run's counters to its own kernel time; this run's
+            # `avg_launch_ms` also spans the alignment launch)
+            scale = 1.0
+            ports = {}
+            if "valu_active" in iss:
+                ports["valu-active"] = iss["valu_active"] * scale
+            for p in ("salu", "lds"):
+                if p + "_issue_frac" in iss:
+                    ports[p + "-issue"] = iss[p + "_issue_frac"] * scale
+            if ports:
+                top = max(ports, key=ports.get)
+                kern["auction"]["roofline"] = {"bound": top, "frac": ports[top],
+                                               "ports": ports, "source": isrc}
+        tr = [kern[k]["traffic"] for k in (("auction",) if fused else ("auction", "gain"))]
+        if fused and n > 64:
+            # the alignment launch that precedes the fused one (its inputs and the
+            # workspace round trip of its results) is in the same timed window
+            am, _ = (committed_profile("pmc_traffic", n, B, align_sym)
+                     if args.formations == 0 else (None, None))
+            tr.append(am["hbm_bytes"] if am else None)
+            kern["auction"]["traffic_align_kernel"] = am["hbm_bytes"] if am else None
+        pipe_traffic = sum(tr) if all(x is not None for x in tr) else None
+        pipe_traffic_src = kern["auction"]["traffic_source"] if pipe_traffic is not None else None
+        gk = kern["auction" if fused else "gain"]
     line = {
         "metric": METRIC,
         "value": world * B / dt_max,
@@ -708,7 +797,8 @@ def main():
             "edges_per_formation_avg": e_avg,
             "cbaa": "all 2N rounds" if args.full_rounds else "exact fixed-point exit",
             "decision_margin": ("tracked" if args.margin else
-                                "not tracked in the timed steps (skip_margin); see `margin`"),
+                                "not tracked in the timed steps (skip_margin)" +
+                                ("; see `margin`" if full else "")),
             "parallelism": f"swarm-sharded x{world}",
             "launch": (f"captured HIP graph of {graph_steps[0]} step(s) (solve + device-side "
                        "stats per step), replayed; one event pair around the timed replays"
@@ -728,24 +818,25 @@ def main():
                     "(HIP events on the solve's stream)",
             "achieved": pipe_ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
             "frac": pipe_ach / HBM_PEAK_GBS,
-            "traffic": pipe_traffic, "traffic_source": pipe_traffic_src,
             "call_ms": call_ms, "bytes_per_call": pipe_bytes,
+        },
+        "gen_s": t_gen,
+    }
+    if full:
+        line["roofline"].update({
+            "traffic": pipe_traffic, "traffic_source": pipe_traffic_src,
             "stream_kernel": {"kernel": gk["kernel"], "achieved": gk["achieved_GBs"],
-                            "frac": gk["frac"], "avg_launch_ms": gk["avg_launch_ms"],
-                            "bytes_per_launch": gk["bytes_per_launch"],
-                            "traffic": gk["traffic"], "traffic_source": gk["traffic_source"]},
+                              "frac": gk["frac"], "avg_launch_ms": gk["avg_launch_ms"],
+                              "bytes_per_launch": gk["bytes_per_launch"],
+                              "traffic": gk["traffic"], "traffic_source": gk["traffic_source"]},
             "note": "frac is the whole call's HBM fraction (the north-star quantity); the "
                     "gain stream carries nearly all algorithmic bytes (" +
                     ("inside the fused auction launch" if fused else "`gain_kernel`") +
                     "); the CBAA rounds are issue-port bound (kernels.auction.roofline)",
             "kernels": kern,
-        },
-        "margin": margin_line,
-        "ca_probe": ca_probe,
-        "stats": stats,
-        "gen_s": t_gen,
-    }
-    if rank == 0 and world == 1 and not args.no_cpu:
+        })
+        line.update(margin=margin_line, ca_probe=ca_probe, stats=stats)
+    if rank == 0 and world == 1 and full and not args.no_cpu:
         nthreads = int(os.environ.get("OMP_NUM_THREADS", os.cpu_count() or 1))
         nthreads = max(1, min(nthreads, os.cpu_count() or 1))
         line["cpu_baseline"] = cpu_baseline(w, out, args.cpu_budget, nthreads)

@@ -4,7 +4,7 @@
 #   [TESTS="tests/a.py tests/b.py"] [PYTEST_K=expr] [BENCH_ARGS="--config c4"] [CMD="python3 scripts/auction_only.py ..."] \
 #     bash scripts/gpu_ab.sh A B ...
 # TESTS: a -m gpu pytest selection run first on the in-tree library (stops on
-# failure). Each variant then runs bench.py (--no-cpu --no-ca-probe
+# failure). Each variant then runs bench.py (--full --no-cpu --no-ca-probe
 # $BENCH_ARGS; one summary line per run) or, with CMD, that command under
 # ACLSWARM_AMD_LIB. OUT (required) names the experiment: outputs go to
 # gpurun_out/$OUT/ab_<V>_<rep>.*, a fresh directory (an existing one is an
@@ -31,7 +31,7 @@ for rep in $(seq 1 ${REPS:-2}); do
       echo "$v $rep: $(tail -1 $D/ab_${v}_$rep.txt)" | tee -a "$D/summary.txt"
       continue
     fi
-    ACLSWARM_AMD_LIB=$lib timeout -k 10 300 python bench.py --no-cpu --no-ca-probe ${BENCH_ARGS} > $D/ab_${v}_$rep.json 2> $D/ab_${v}_$rep.err || { echo "bench $v failed"; tail -20 $D/ab_${v}_$rep.err; exit 1; }
+    ACLSWARM_AMD_LIB=$lib timeout -k 10 300 python bench.py --full --no-cpu --no-ca-probe ${BENCH_ARGS} > $D/ab_${v}_$rep.json 2> $D/ab_${v}_$rep.err || { echo "bench $v failed"; tail -20 $D/ab_${v}_$rep.err; exit 1; }
     python -c "
 import json
 d = json.load(open('$D/ab_${v}_$rep.json'))

@@ -8,6 +8,9 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout
 grep -cE "PASSED" gpurun_out/pytest_gpu.log; tail -2 gpurun_out/pytest_gpu.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 || { echo "smoke failed"; tail -30 gpurun_out/smoke.log; exit 1; }
 cat gpurun_out/smoke.log
-timeout -k 10 600 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err || { echo "bench failed"; tail -30 gpurun_out/bench.err; exit 1; }
-cat gpurun_out/bench.json
+# (the --full line: per-kernel times, margin A/B, crowded probe, CPU baseline; kept in
+# $BENCH_DIR when that is set)
+BD=${BENCH_DIR:-$(mktemp -d)}
+timeout -k 10 600 python bench.py --full > $BD/bench.json 2> $BD/bench.err || { echo "bench failed"; tail -30 $BD/bench.err; exit 1; }
+cat $BD/bench.json
 bash scripts/gpu_prof.sh && bash scripts/gpu_pmc.sh

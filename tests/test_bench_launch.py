@@ -2,7 +2,7 @@
 directly spawns its N ranks (the torchrun environment contract) before any
 GPU call; --dry-run runs the same launch + gather + max-over-ranks timing on
 gloo with synthetic outputs, so the path the driver's SCALE run takes is
-exercised without a GPU."""
+exercised without a GPU; --dump-outputs and its seeded row sample likewise."""
 import json
 import os
 import subprocess
@@ -66,3 +66,49 @@ def test_graph_group_times_exactly_the_steps():
         for G in range(0, 15):
             g = bench.graph_group(G, K)
             assert K % g == 0 and 1 <= g <= max(1, G)
+
+
+def test_dump_outputs_dry_run(tmp_path):
+    """--dump-outputs writes the gathered outputs of the last step as float
+    .npy files, the status records field by field; --full is accepted."""
+    import numpy as np
+    d = tmp_path / "dump"
+    r = _run(["--gpus", "1", "--dry-run", "--steps", "2", "--warmup", "1", "--B", "64", "--full",
+              "--dump-outputs", str(d)])
+    assert r.returncode == 0, r.stderr
+    line = _json_lines(r.stdout)[0]
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    P = np.load(d / "P_out.npy")
+    assert P.dtype == np.float32 and P.shape == (64, 100)
+    assert (P == np.arange(100, dtype=np.float32)).all()
+    assert (np.load(d / "sample_rows.npy") == np.arange(64)).all()
+    eff = np.load(d / "status_eff_rounds.npy")
+    assert eff.dtype == np.float32 and (eff == 3).all()
+    assert np.load(d / "status_flags.npy").dtype == np.float64
+    assert (np.load(d / "status_margin.npy") == np.float32(0.5)).all()
+    total = sum(f.stat().st_size for f in d.iterdir())
+    assert total <= 64 << 20
+
+
+def test_dump_outputs_sample_is_fixed(tmp_path, monkeypatch):
+    """Above the byte budget a sorted sample of rows is written, the same
+    rows for the same seed, and every array holds those rows."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    B = 1000
+    x = torch.arange(B * 6, dtype=torch.float64).reshape(B, 2, 3)
+    k = torch.arange(B, dtype=torch.int32)
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 100 * (8 + 48 + 8))
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), {"x": x, "k": k}, seed=5)
+    bench.dump_outputs(str(tmp_path / "c"), {"x": x, "k": k}, seed=6)
+    rows = np.load(tmp_path / "a" / "sample_rows.npy")
+    assert rows.shape == (100,) and (np.diff(rows) > 0).all()
+    assert (rows == np.load(tmp_path / "b" / "sample_rows.npy")).all()
+    assert not (rows == np.load(tmp_path / "c" / "sample_rows.npy")).all()
+    xa, ka = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "a" / "k.npy")
+    assert xa.dtype == np.float64 and ka.dtype == np.float64
+    assert (ka == rows).all() and (xa == x.numpy()[rows.astype(int)]).all()
+    assert (xa == np.load(tmp_path / "b" / "x.npy")).all()

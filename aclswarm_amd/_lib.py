@@ -36,7 +36,7 @@ EXPORTS = (
     "acl_formations_init", "acl_max_vehicles", "acl_abi_version", "acl_solve_workspace_bytes", "acl_solve_batch", "acl_swarm_stats", "acl_count_edges", "acl_pack_adjacency",
     "acl_pack_gains", "acl_gain_planes", "acl_pack_gains_planes", "acl_tile_gains", "acl_admm_solve_batch", "acl_device_count", "acl_set_device",
     "acl_control_batch", "acl_write_assignment_log", "acl_read_assignment_log",
-    "acl_hungarian_batch", "acl_cbaa_step_batch",
+    "acl_hungarian_batch", "acl_cbaa_step_batch", "acl_vehicle_start_batch",
     "acl_default_episode_params", "acl_episode_workspace_bytes", "acl_episode_batch",
     "acl_default_trial_params", "acl_trial_workspace_bytes", "acl_trial_init", "acl_trial_batch",
     "acl_generate_formation_groups",
@@ -108,6 +108,14 @@ class CbaaStepArgs(ct.Structure):
     _fields_ = [("V", ct.c_int32), ("K", ct.c_int32)] + [(n, ct.c_void_p) for n in (
         "fidx", "vehid", "q", "Rt", "start", "price", "who", "cand_off", "cand_vehid",
         "cand_price", "cand_who", "task", "flags")]
+
+
+class VehicleStartArgs(ct.Structure):
+    """acl_vehicle_start_args_t (added within ABI 11): one vehicle's auction
+    start, alignment under its own assignment and the START bid
+    (auctioneer.cpp:78-120,347-415,448-465,517-549)."""
+    _fields_ = [("V", ct.c_int32), ("S", ct.c_int32)] + [(n, ct.c_void_p) for n in (
+        "fidx", "vehid", "qidx", "q", "Pt", "Rt", "price", "who", "task", "flags")]
 
 
 class EpisodeParams(ct.Structure):
@@ -255,6 +263,9 @@ def lib():
     L.acl_hungarian_batch.restype = ct.c_int
     L.acl_cbaa_step_batch.argtypes = [ct.POINTER(Formations), ct.POINTER(CbaaStepArgs), VP]
     L.acl_cbaa_step_batch.restype = ct.c_int
+    L.acl_vehicle_start_batch.argtypes = [ct.POINTER(Formations), ct.POINTER(VehicleStartArgs),
+                                          VP]
+    L.acl_vehicle_start_batch.restype = ct.c_int
     L.acl_write_assignment_log.argtypes = [ct.c_char_p, I32, VP, VP, VP, VP, VP, VP]
     L.acl_write_assignment_log.restype = ct.c_int
     L.acl_read_assignment_log.argtypes = [ct.c_char_p, ct.POINTER(I32), VP, VP, VP, VP, VP, VP]

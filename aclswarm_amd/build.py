@@ -15,10 +15,14 @@ ROOT = os.path.dirname(HERE)
 # C++ facade exerciser (include/aclswarm_amd.hpp), run by tests/test_gpu_facade.py
 DRIVER_SRC = os.path.join(ROOT, "tests", "facade_driver.cpp")
 DRIVER = os.path.join(HERE, "lib", "libfacade_driver.so")
+# the exchange-mode start of the facade (fleets with own assignments, start
+# latency), run by tests/test_gpu_facade_start.py
+START_DRIVER_SRC = os.path.join(ROOT, "tests", "facade_start_driver.cpp")
+START_DRIVER = os.path.join(HERE, "lib", "libfacade_start_driver.so")
 # the codegen-compatible ADMM entry points driven as aclswarm/src/admm.cpp does
 CG_DRIVER_SRC = os.path.join(ROOT, "tests", "codegen_driver.cpp")
 CG_DRIVER = os.path.join(HERE, "lib", "libcodegen_driver.so")
-SOURCES = ["solve.hip", "auction.hip", "solve_wide.hip", "control.hip", "admm.hip", "hungarian.hip", "cbaa_step.hip", "episode.hip",
+SOURCES = ["solve.hip", "auction.hip", "solve_wide.hip", "control.hip", "admm.hip", "hungarian.hip", "cbaa_step.hip", "vehicle_start.hip", "episode.hip",
            "trial.hip", "formation_gen.hip", "api.cpp"]
 # The generated ADMM library's C++ entry points (ADMMGainDesign3D and the
 # generic MATLAB-Coder emx utilities) live in their own shim library linked to
@@ -93,12 +97,14 @@ def _gxx_driver(src, out, incs, deps, force, verbose, libs=("aclswarm_amd",)):
 
 def build_driver(force=False, verbose=False):
     """g++ against the library, found next to the binary ($ORIGIN): the C++
-    facade exerciser and the codegen-entry-point driver."""
+    facade exercisers and the codegen-entry-point driver."""
     inc = os.path.join(ROOT, "include")
     build_codegen(force, verbose)
     _gxx_driver(CG_DRIVER_SRC, CG_DRIVER, [os.path.join(inc, "codegen_admm")],
                 [CG_DRIVER_SRC, OUT, CODEGEN_OUT, os.path.join(inc, "aclswarm_amd_codegen.h")],
                 force, verbose, libs=("aclswarm_amd_codegen", "aclswarm_amd"))
+    _gxx_driver(START_DRIVER_SRC, START_DRIVER, [inc],
+                [START_DRIVER_SRC, OUT, os.path.join(inc, "aclswarm_amd.hpp")], force, verbose)
     return _gxx_driver(DRIVER_SRC, DRIVER, [inc],
                        [DRIVER_SRC, OUT, os.path.join(inc, "aclswarm_amd.hpp")], force, verbose)
 

@@ -26,6 +26,7 @@
 // with -ffp-contract=off), so the floats equal the batched auction's prices
 // bit for bit.
 #include "common.h"
+#include "cbaa_select_dev.h"  // kStepWaves, step_price, step_select
 
 #include "../../include/aclswarm_amd.h"
 
@@ -50,23 +51,6 @@ struct StepParams {
   int32_t* task;
   int32_t* flags;
 };
-
-constexpr int kStepWaves = 4;  // vehicles per workgroup (one per wave)
-
-// getPrice of task j for a vehicle at (qx, qy, qz) with alignment o[6]:
-// aligned = ((R p^T).colwise() + t)^T, R = [R2 0; 0 0 1] (auctioneer.cpp:
-// 400-414), then (float)(1 / (||q - aligned|| + 1e-8)) with IEEE sqrt and
-// division -- the oracle's orc_prices_rows expression term for term
-__device__ __forceinline__ float step_price(const double* o, double qx, double qy, double qz,
-                                            const double* pj) {
-  const double px = pj[0], py = pj[1], pz = pj[2];
-  const double ax = ((o[0] * px + o[1] * py) + 0.0 * pz) + o[4];
-  const double ay = ((o[2] * px + o[3] * py) + 0.0 * pz) + o[5];
-  const double az = ((0.0 * px + 0.0 * py) + 1.0 * pz) + 0.0;
-  const double dx = qx - ax, dy = qy - ay, dz = qz - az;
-  const double nrm = __builtin_sqrt((dx * dx + dy * dy) + dz * dz);
-  return (float)(1.0 / (nrm + 1e-8));
-}
 
 template <int S>
 __global__ void __launch_bounds__(64 * kStepWaves) cbaa_step_kernel(const StepParams P) {
@@ -136,35 +120,7 @@ __global__ void __launch_bounds__(64 * kStepWaves) cbaa_step_kernel(const StepPa
     const double* q = P.q + (size_t)k * 3;
     const double qx = q[0], qy = q[1], qz = q[2];
     const double* pf = P.p + (size_t)f * n * 3;
-    float c[S];
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      const int j = lane + 64 * s;
-      c[s] = 0.0f;
-      if (j < n) {
-        const float x = step_price(o, qx, qy, qz, pf + 3 * j);
-        if (x > 0.0f && x > own_p[s]) {
-          c[s] = x;
-          const unsigned b = __float_as_uint(x);
-          best = b > best ? b : best;
-        }
-      }
-    }
-    best = wave_max_u32(best);
-    if (best != 0u) {
-      // the lowest task holding it: each lane's lowest slot, then a wave minimum
-      int jmin = 0x7FFFFFFF;
-#pragma unroll
-      for (int s = S - 1; s >= 0; --s) {
-        const int j = lane + 64 * s;
-        if (j < n && __float_as_uint(c[s]) == best) jmin = j;
-      }
-      for (int off = 32; off >= 1; off >>= 1) {
-        const int o2 = __shfl_xor(jmin, off);
-        jmin = o2 < jmin ? o2 : jmin;
-      }
-      task = jmin;
-    }
+    task = step_select<S>(o, qx, qy, qz, pf, n, lane, own_p, best);
   }
   // (:538-541) the bid on the selected task; the merged table elsewhere
 #pragma unroll

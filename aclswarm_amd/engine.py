@@ -382,6 +382,69 @@ def cbaa_step(table, fidx, vehid, q, Rt, start, price, who, cand_off, cand_vehid
     return task, flags
 
 
+def vehicle_start(table, fidx, vehid, q, Pt, qidx=None, want_bid=True, stream=None):
+    """acl_vehicle_start_batch (added within ABI 11): what each of V vehicles
+    does when an auction starts (auctioneer.cpp:78-120) -- the alignment to
+    its closed neighbourhood under its OWN assignment (:347-415) and, with
+    want_bid, its START bid (:448-465, 517-549). Device tensors: fidx / vehid
+    [V] i32, q [S][n][3] f64 (S snapshots), Pt [V][n] int16 (uint16 bits, as
+    solve takes P_in): vehicle k's row, formation point -> vehicle; qidx [V]
+    i32 the snapshot of each vehicle (None: snapshot k, S >= V). Returns a
+    dict of device tensors: Rt [V][6] f64, flags [V] i32 (0x02 SELECTED, 0x10
+    BAD_INPUT) and, with want_bid, price [V][n] f32, who [V][n] i32, task [V]
+    i32. Raises ValueError on a malformed argument before anything runs."""
+    n = table.n
+    for name, t in (("fidx", fidx), ("vehid", vehid), ("q", q), ("Pt", Pt)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"vehicle_start: {name} must be a torch tensor")
+    if vehid.dim() != 1:
+        raise ValueError("vehicle_start: vehid must have shape (V,)")
+    V = int(vehid.shape[0])
+    dev = vehid.device
+    if q.dim() != 3 or tuple(q.shape[1:]) != (n, 3):
+        raise ValueError(f"vehicle_start: q must have shape (S, {n}, 3)")
+    S = int(q.shape[0])
+    want = {"fidx": (fidx, (torch.int32,), (V,)), "vehid": (vehid, (torch.int32,), (V,)),
+            "q": (q, (torch.float64,), (S, n, 3)),
+            "Pt": (Pt, (torch.int16, torch.uint16), (V, n))}
+    if qidx is not None:
+        want["qidx"] = (qidx, (torch.int32,), (V,))
+    for name, (t, dts, shape) in want.items():
+        if not isinstance(t, torch.Tensor) or t.dtype not in dts or tuple(t.shape) != shape \
+                or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"vehicle_start: {name} must be a contiguous {dts[0]} tensor of "
+                             f"shape {shape} on {dev}")
+    if qidx is None and S < V:
+        raise ValueError(f"vehicle_start: qidx is None and q holds S = {S} < V = {V} snapshots")
+    if table.p.device != dev:
+        raise ValueError(f"vehicle_start: the formation table is on {table.p.device}, the "
+                         f"vehicles on {dev}")
+    if dev.type != "cuda":
+        raise ValueError(f"vehicle_start: the tensors must be on a CUDA device, not {dev}")
+    lib = L.lib()
+    out = {"Rt": torch.empty((V, 6), dtype=torch.float64, device=dev),
+           "flags": torch.empty((V,), dtype=torch.int32, device=dev)}
+    if want_bid:
+        out["price"] = torch.empty((V, n), dtype=torch.float32, device=dev)
+        out["who"] = torch.empty((V, n), dtype=torch.int32, device=dev)
+        out["task"] = torch.empty((V,), dtype=torch.int32, device=dev)
+    a = L.VehicleStartArgs()
+    a.V = V
+    a.S = S
+    a.fidx = fidx.data_ptr(); a.vehid = vehid.data_ptr(); a.q = q.data_ptr()
+    a.qidx = qidx.data_ptr() if qidx is not None else None
+    a.Pt = Pt.data_ptr(); a.Rt = out["Rt"].data_ptr(); a.flags = out["flags"].data_ptr()
+    if want_bid:
+        a.price = out["price"].data_ptr(); a.who = out["who"].data_ptr()
+        a.task = out["task"].data_ptr()
+    F = table.struct()
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    L.check(lib.acl_vehicle_start_batch(ct.byref(F), ct.byref(a), ct.c_void_p(stream)),
+            "acl_vehicle_start_batch")
+    return out
+
+
 def write_assignment_log(path, q, adj, lastP, p, align_Rt, P):
     """Auctioneer::logAssignment's binary record (auctioneer.cpp:577-597),
     host arrays: q, p [n][3]; adj [n][n] (adj[i][j] = adjmat(i,j)); lastP, P

@@ -510,6 +510,51 @@ typedef struct {
 acl_status_t acl_cbaa_step_batch(const acl_formations_t* formations,
                                  const acl_cbaa_step_args_t* args, void* stream);
 
+/* ---- one vehicle's auction start, batched (added within ABI 11) -----------
+ * What Auctioneer::start does for one vehicle (auctioneer.cpp:78-120): it
+ * aligns the formation to the vehicle's closed neighbourhood under the
+ * vehicle's OWN assignment (alignFormation, :347-415) and makes its START
+ * bid (reset, :448-465; selectTaskAssignment and getPrice, :517-549) -- the
+ * entry a vehicle of the message protocol above needs before its first
+ * acl_cbaa_step_batch, without a whole-swarm acl_solve_batch. An added
+ * symbol: ACL_ABI_VERSION stays 11 (no existing struct or call changed). For
+ * vehicle k of V (any swarms, one formation table):
+ *   - its row Pt[k] (formation point -> vehicle, the vehicle's Pt_; the
+ *     meaning of one acl_solve_args_t::P_rows row) puts it at the point i
+ *     with Pt[k][i] == vehid[k]; the members are the points j = i and
+ *     adj(i, j), ascending, src p_j.xy, dst the xy of vehicle Pt[k][j] in
+ *     snapshot qidx[k];
+ *   - Rt[k] = Eigen::umeyama(src, dst, false) in acl_solve_batch's
+ *     arithmetic: the same bits as its align_Rt row of that vehicle;
+ *   - with price / who / task: the table is reset (price 0, who -1) and the
+ *     START bid made from Rt[k] and the vehicle's own position -- exactly what
+ *     acl_cbaa_step_batch with start = 1 gives from the same Rt.
+ * Device pointers as commented in the struct. flags[k]: ACL_CBAA_SELECTED, or
+ * ACL_CBAA_BAD_INPUT when vehid, fidx or qidx is out of range or the row is
+ * not a permutation of 0..n-1: then task[k] = -1, Rt[k] is NaN and the
+ * price / who rows are left as they were. A non-finite member position is
+ * not an error: Rt[k] is NaN, the table is reset and task[k] = -1 (the
+ * reference's arithmetic). price, who and task are all given or all NULL
+ * (NULL: alignment only). n in [1, 512]. Stream-ordered, no workspace, never
+ * synchronises. */
+typedef struct {
+  int32_t V;              /* vehicles */
+  int32_t S;              /* snapshots: rows of q */
+  const int32_t* fidx;    /* [V]   formation of vehicle k's swarm */
+  const int32_t* vehid;   /* [V]   its id in its swarm, < n */
+  const int32_t* qidx;    /* [V]   its snapshot, < S; NULL: snapshot k (then S >= V) */
+  const double* q;        /* [S][n][3] */
+  const uint16_t* Pt;     /* [V][n] its own assignment, formation point -> vehicle */
+  double* Rt;             /* [V][6] out {R00,R01,R10,R11,tx,ty} */
+  float* price;           /* [V][n] out, optional: the START bid's table */
+  int32_t* who;           /* [V][n] out, with price */
+  int32_t* task;          /* [V]   out, with price: the task taken, -1 none */
+  int32_t* flags;         /* [V]   out: ACL_CBAA_SELECTED | ACL_CBAA_BAD_INPUT */
+} acl_vehicle_start_args_t;
+
+acl_status_t acl_vehicle_start_batch(const acl_formations_t* formations,
+                                     const acl_vehicle_start_args_t* args, void* stream);
+
 /* ---- closed-loop batched episodes ---------------------
  * B swarms flown for `steps` control periods in lockstep: the discrete-time
  * model of one vehicle's node graph (CoordinationROS + Safety) with a

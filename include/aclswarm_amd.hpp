@@ -43,8 +43,9 @@
  *    is true whenever start() is not running.
  *    Exchange mode (setBidExchange(true), ABI 11) is the reference's message
  *    protocol instead, for fleets that mix these objects with other
- *    vehicles' Auctioneers: start() aligns on the GPU (acl_solve_batch, this
- *    vehicle's align_Rt row), makes the START bid and sends it (iter 0);
+ *    vehicles' Auctioneers: start() aligns this vehicle under its own
+ *    assignment and makes the START bid on the GPU (acl_vehicle_start_batch,
+ *    V = 1: no whole-swarm solve) and sends it (iter 0);
  *    enqueueBid queues neighbours' bids, tick() processes one as processBid
  *    does (auctioneer.cpp:182-306: iteration buckets, the START-bid bucket,
  *    bidIterComplete over the neighbours of this vehicle's own assignment),
@@ -655,27 +656,80 @@ class Auctioneer {
     if (send_bid_) send_bid_((uint32_t)auctionid_, (uint32_t)biditer_, std::make_shared<const Bid>(bid_));
   }
 
-  /* start (auctioneer.cpp:78-120): alignment on the GPU, the START bid */
+  /* start (auctioneer.cpp:78-120): this vehicle's alignment under its own
+   * assignment and its START bid in one launch (acl_vehicle_start_batch,
+   * V = 1) -- one staging image up, one copy back. An assignment that is not
+   * a permutation (setAssignmentIndices does not validate) starts nothing:
+   * ACL_ERR_INVALID_ARG, no bid, the vehicle stays idle. */
   void start_exchange(const double* q_colmajor) {
     reset_x();
     bids_curr_ = bids_zero_;
     bids_zero_.clear();
+    auctionid_++;
+    if (verbose_)  // auctioneer.cpp:110-115
+      std::cout << std::endl << "********* Starting auction " << auctionid_ << " *********"
+                << std::endl << std::endl;
+    const int n = n_;
+    int32_t out[2] = {-1, 0};  // task, flags
     try {
-      const AuctionOut r = run_auction(q_colmajor);  // this vehicle's align_Rt row
-      q_self_[0] = r.q[(size_t)3 * vehid_];
-      q_self_[1] = r.q[(size_t)3 * vehid_ + 1];
-      q_self_[2] = r.q[(size_t)3 * vehid_ + 2];
-      std::copy(r.Rt.begin() + (size_t)6 * vehid_, r.Rt.begin() + (size_t)6 * vehid_ + 6, rt_self_);
-      step(true);
-      last_status_ = ACL_OK;
-      last_error_.clear();
+      // the image: the snapshot (xyz rows), then what comes back -- Rt, the
+      // table (price, who), task and flags -- then the ids and the row
+      const size_t o_q = 0, o_rt = (size_t)24 * n, o_price = o_rt + 48,
+                   o_who = o_price + (size_t)4 * n, o_out = o_who + (size_t)4 * n,
+                   o_i = o_out + 8, o_pt = o_i + 8, total = o_pt + (size_t)2 * n;
+      std::vector<unsigned char> h(total, 0);
+      const std::vector<double> q = detail::rows_xyz(n, q_colmajor);
+      const int32_t ids[2] = {0, (int32_t)vehid_};  // fidx, vehid
+      std::memcpy(&h[o_q], q.data(), (size_t)24 * n);
+      std::memcpy(&h[o_i], ids, 8);
+      for (int j = 0; j < n; ++j) {
+        const uint16_t u = Pt_[j];
+        std::memcpy(&h[o_pt + (size_t)2 * j], &u, 2);
+      }
+      x_stage_.upload(h.data(), total);
+      unsigned char* d = x_stage_.as<unsigned char>();
+      acl_vehicle_start_args_t a;
+      std::memset(&a, 0, sizeof(a));
+      a.V = 1;
+      a.S = 1;
+      a.fidx = reinterpret_cast<const int32_t*>(d + o_i);
+      a.vehid = reinterpret_cast<const int32_t*>(d + o_i) + 1;
+      a.qidx = nullptr;
+      a.q = reinterpret_cast<const double*>(d + o_q);
+      a.Pt = reinterpret_cast<const uint16_t*>(d + o_pt);
+      a.Rt = reinterpret_cast<double*>(d + o_rt);
+      a.price = reinterpret_cast<float*>(d + o_price);
+      a.who = reinterpret_cast<int32_t*>(d + o_who);
+      a.task = reinterpret_cast<int32_t*>(d + o_out);
+      a.flags = reinterpret_cast<int32_t*>(d + o_out) + 1;
+      const acl_formations_t F = form_.table();
+      detail::check(acl_vehicle_start_batch(&F, &a, nullptr));
+      detail::check(acl_memcpy_d2h(&h[o_rt], d + o_rt, o_i - o_rt, nullptr));
+      detail::check(acl_stream_synchronize(nullptr));
+      std::memcpy(out, &h[o_out], 8);
+      if (!(out[1] & ACL_CBAA_BAD_INPUT)) {
+        std::memcpy(q_self_, &q[(size_t)3 * vehid_], 24);
+        std::memcpy(rt_self_, &h[o_rt], 48);
+        std::memcpy(bid_.price.data(), &h[o_price], (size_t)4 * n);
+        std::vector<int32_t> who(n);
+        std::memcpy(who.data(), &h[o_who], (size_t)4 * n);
+        bid_.who.assign(who.begin(), who.end());
+      }
     } catch (const std::exception& e) {
       last_status_ = ACL_ERR_HIP;
       last_error_ = e.what();
       reset_x();
       return;
     }
-    auction_open_ = true;  // (run_auction counted the auction id)
+    if (out[1] & ACL_CBAA_BAD_INPUT) {
+      last_status_ = ACL_ERR_INVALID_ARG;
+      last_error_ = "Auctioneer::start: this vehicle's assignment is not a permutation";
+      reset_x();
+      return;
+    }
+    last_status_ = ACL_OK;
+    last_error_.clear();
+    auction_open_ = true;
     notifySendBid();
   }
 
@@ -707,7 +761,7 @@ class Auctioneer {
                 << static_cast<int>(pkt.vehid) << std::endl;
     if (!bidIterComplete()) return;
     try {
-      step(false);  // updateTaskAssignment, then selectTaskAssignment if outbid
+      step();  // updateTaskAssignment, then selectTaskAssignment if outbid
     } catch (const std::exception& e) {
       last_status_ = ACL_ERR_HIP;
       last_error_ = e.what();
@@ -729,24 +783,22 @@ class Auctioneer {
     }
   }
 
-  /* One tally of this vehicle on the GPU (acl_cbaa_step_batch, V = 1): the
-   * START bid, or the candidates = bids_curr_ with its own bid inserted
-   * (:475, std::map order) */
-  void step(bool start) {
+  /* One tally of this vehicle on the GPU (acl_cbaa_step_batch, V = 1) over
+   * the candidates = bids_curr_ with its own bid inserted (:475, std::map
+   * order); the START bid is start_exchange's */
+  void step() {
     const int n = n_;
     std::vector<int32_t> cv;
     std::vector<float> cp;
     std::vector<int32_t> cw;
-    if (!start) {
-      std::map<vehidx_t, Bid> cand = bids_curr_;
-      cand.insert({vehid_, bid_});
-      for (const auto& kv : cand) {
-        if ((int)kv.second.price.size() != n || (int)kv.second.who.size() != n)
-          throw std::runtime_error("Auctioneer: a bid's tables are not n long");
-        cv.push_back((int32_t)kv.first);
-        cp.insert(cp.end(), kv.second.price.begin(), kv.second.price.end());
-        cw.insert(cw.end(), kv.second.who.begin(), kv.second.who.end());
-      }
+    std::map<vehidx_t, Bid> cand = bids_curr_;
+    cand.insert({vehid_, bid_});
+    for (const auto& kv : cand) {
+      if ((int)kv.second.price.size() != n || (int)kv.second.who.size() != n)
+        throw std::runtime_error("Auctioneer: a bid's tables are not n long");
+      cv.push_back((int32_t)kv.first);
+      cp.insert(cp.end(), kv.second.price.begin(), kv.second.price.end());
+      cw.insert(cw.end(), kv.second.who.begin(), kv.second.who.end());
     }
     const int K = (int)cv.size();
     // one staging image each way (one copy up, one down): doubles first,
@@ -768,12 +820,10 @@ class Auctioneer {
     }
     std::memcpy(&h[o_i], ids, 8);
     std::memcpy(&h[o_off], off, 8);
-    h[o_st] = start ? 1 : 0;
-    if (K) {
-      std::memcpy(&h[o_cv], cv.data(), (size_t)4 * K);
-      std::memcpy(&h[o_cp], cp.data(), cp.size() * 4);
-      std::memcpy(&h[o_cw], cw.data(), cw.size() * 4);
-    }
+    h[o_st] = 0;  // a bid iteration
+    std::memcpy(&h[o_cv], cv.data(), (size_t)4 * K);
+    std::memcpy(&h[o_cp], cp.data(), cp.size() * 4);
+    std::memcpy(&h[o_cw], cw.data(), cw.size() * 4);
     x_stage_.upload(h.data(), total);
     unsigned char* d = x_stage_.as<unsigned char>();
     acl_cbaa_step_args_t a;
@@ -788,9 +838,9 @@ class Auctioneer {
     a.price = reinterpret_cast<float*>(d + o_price);
     a.who = reinterpret_cast<int32_t*>(d + o_who);
     a.cand_off = reinterpret_cast<const int32_t*>(d + o_off);
-    a.cand_vehid = K ? reinterpret_cast<const int32_t*>(d + o_cv) : nullptr;
-    a.cand_price = K ? reinterpret_cast<const float*>(d + o_cp) : nullptr;
-    a.cand_who = K ? reinterpret_cast<const int32_t*>(d + o_cw) : nullptr;
+    a.cand_vehid = reinterpret_cast<const int32_t*>(d + o_cv);
+    a.cand_price = reinterpret_cast<const float*>(d + o_cp);
+    a.cand_who = reinterpret_cast<const int32_t*>(d + o_cw);
     a.task = reinterpret_cast<int32_t*>(d + o_out);
     a.flags = reinterpret_cast<int32_t*>(d + o_out) + 1;
     const acl_formations_t F = form_.table();
@@ -816,7 +866,7 @@ class Auctioneer {
   std::vector<BidPkt> rxbids_;  // FIFO (std::queue in the reference)
   std::vector<uint8_t> adj_;    // AdjMat, column-major
   double q_self_[3] = {0.0, 0.0, 0.0}, rt_self_[6] = {1.0, 0.0, 0.0, 1.0, 0.0, 0.0};
-  detail::DeviceBuffer x_stage_;  // acl_cbaa_step_batch's staging image (step())
+  detail::DeviceBuffer x_stage_;  // staging image of start_exchange() and step()
   std::vector<vehidx_t> P_, Pt_;
   int auctionid_ = 0;
   bool auction_open_ = false;

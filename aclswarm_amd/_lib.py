@@ -37,6 +37,7 @@ EXPORTS = (
     "acl_pack_gains", "acl_gain_planes", "acl_pack_gains_planes", "acl_tile_gains", "acl_admm_solve_batch", "acl_device_count", "acl_set_device",
     "acl_control_batch", "acl_write_assignment_log", "acl_read_assignment_log",
     "acl_hungarian_batch", "acl_cbaa_step_batch", "acl_vehicle_start_batch",
+    "acl_fleet_workspace_bytes", "acl_fleet_auction_batch",
     "acl_default_episode_params", "acl_episode_workspace_bytes", "acl_episode_batch",
     "acl_default_trial_params", "acl_trial_workspace_bytes", "acl_trial_init", "acl_trial_batch",
     "acl_generate_formation_groups",
@@ -116,6 +117,26 @@ class VehicleStartArgs(ct.Structure):
     (auctioneer.cpp:78-120,347-415,448-465,517-549)."""
     _fields_ = [("V", ct.c_int32), ("S", ct.c_int32)] + [(n, ct.c_void_p) for n in (
         "fidx", "vehid", "qidx", "q", "Pt", "Rt", "price", "who", "task", "flags")]
+
+
+class FleetAuctionArgs(ct.Structure):
+    """acl_fleet_auction_args_t (added within ABI 11): the message-level CBAA of
+    B swarms, queues and buckets on the device (auctioneer.cpp:66-306,419-465)."""
+    _fields_ = [(n, ct.c_int32) for n in ("B", "ticks", "max_iter", "queue_cap")] + [
+        (n, ct.c_void_p) for n in (
+            "fidx", "q", "cmd", "Pt", "open", "invalid", "just_received", "biditer", "price",
+            "who", "Rt", "final_price", "final_who", "done_tick", "vflags", "n_thrown",
+            "n_tally", "queue_len", "status", "hist_biditer", "hist_open", "workspace")] + [
+        ("workspace_bytes", ct.c_size_t)]
+
+
+FLEET_NONE, FLEET_START, FLEET_FLUSH = 0, 1, 2
+FLEET_QUIESCENT, FLEET_OVERFLOW, FLEET_BAD_INPUT = 0x1, 0x2, 0x4
+FLEET_V_STARTED, FLEET_V_BAD_ROW, FLEET_V_CONSENSUS = 0x01, 0x02, 0x04
+FLEET_V_ADOPTED, FLEET_V_INVALID, FLEET_V_OVERFLOW = 0x08, 0x10, 0x20
+FLEET_MAX_N = 128
+
+FLEET_STATUS_DTYPE = np.dtype([(k, "<i4") for k in ("ticks_run", "n_open", "n_queued", "flags")])
 
 
 class EpisodeParams(ct.Structure):
@@ -266,6 +287,11 @@ def lib():
     L.acl_vehicle_start_batch.argtypes = [ct.POINTER(Formations), ct.POINTER(VehicleStartArgs),
                                           VP]
     L.acl_vehicle_start_batch.restype = ct.c_int
+    L.acl_fleet_workspace_bytes.argtypes = [I32, I32, I32]
+    L.acl_fleet_workspace_bytes.restype = SZ
+    L.acl_fleet_auction_batch.argtypes = [ct.POINTER(Formations), ct.POINTER(FleetAuctionArgs),
+                                          VP]
+    L.acl_fleet_auction_batch.restype = ct.c_int
     L.acl_write_assignment_log.argtypes = [ct.c_char_p, I32, VP, VP, VP, VP, VP, VP]
     L.acl_write_assignment_log.restype = ct.c_int
     L.acl_read_assignment_log.argtypes = [ct.c_char_p, ct.POINTER(I32), VP, VP, VP, VP, VP, VP]

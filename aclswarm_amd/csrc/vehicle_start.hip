@@ -25,7 +25,7 @@
 //      acl_cbaa_step_batch runs with start = 1.
 #include "common.h"
 #include "cbaa_select_dev.h"
-#include "umeyama_dev.h"
+#include "own_row_dev.h"  // own_row_check, own_row_align (umeyama_dev.h)
 
 #include "../../include/aclswarm_amd.h"
 
@@ -77,24 +77,7 @@ __global__ void __launch_bounds__(64 * StartWaves<SL>::value)
   bool bad = v < 0 || v >= n || f < 0 || f >= P.F || sn < 0 || sn >= P.S;
   const uint16_t* row = P.Pt + (size_t)k * n;
   int u[SL];
-#pragma unroll
-  for (int s = 0; s < SL; ++s) {
-    const int j = lane + 64 * s;
-    u[s] = j < n ? (int)row[j] : 0;
-    if (j < n) {
-      if (u[s] >= n) bad = true;
-      else inv[u[s]] = (unsigned short)j;
-    }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-#pragma unroll
-  for (int s = 0; s < SL; ++s) {
-    const int j = lane + 64 * s;
-    // (u < n: inv[u] was written, by this lane or by the duplicate's)
-    if (j < n && u[s] < n && (int)inv[u[s]] != j) bad = true;
-  }
+  if (own_row_check<SL>(row, n, lane, inv, u)) bad = true;
   bad = __any(bad);
   if (bad) {
     if (lane == 0) {
@@ -109,70 +92,14 @@ __global__ void __launch_bounds__(64 * StartWaves<SL>::value)
   // the vehicle's point: the row is a permutation, so inv[v] is the one i
   // with Pt[i] == v
   const int i = __builtin_amdgcn_readfirstlane((int)inv[v]);
-  // 2. members of formation row i's closed neighbourhood, ascending
+  // 2., 3. members of formation row i's closed neighbourhood and the
+  // alignment over them (own_row_dev.h)
   const int NW = (n + 63) >> 6;
   const unsigned long long* adjrow = P.adj + ((size_t)f * n + i) * NW;
   const double* pf = P.p + (size_t)f * n * 3;
   const double* qs = P.q + (size_t)sn * n * 3;
-  int km = 0;
-#pragma unroll
-  for (int s = 0; s < SL; ++s) {
-    const int j = lane + 64 * s;
-    bool m = false;
-    if (s < NW) {  // wave-uniform
-      unsigned long long w = adjrow[s];
-      if (s == (i >> 6)) w |= 1ull << (i & 63);
-      m = j < n && ((w >> lane) & 1ull) != 0ull;
-    }
-    const unsigned long long b = __ballot(m);
-    if (m) {
-      const int pos = km + (int)__builtin_amdgcn_mbcnt_hi(
-                               (unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-      const double* qu = qs + 3 * u[s];
-      st[4 * pos + 0] = pf[3 * j];
-      st[4 * pos + 1] = pf[3 * j + 1];
-      st[4 * pos + 2] = qu[0];
-      st[4 * pos + 3] = qu[1];
-    }
-    km += __popcll(b);
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  // 3. alignment: align_own_row's sums over the km >= 1 staged members, in
-  // order (never a tree: the sums are order-dependent)
-  double s0 = -0.0, s1 = -0.0, s2 = -0.0, s3 = -0.0;
-  for (int m = 0; m < km; ++m) {
-    s0 = s0 + st[4 * m];
-    s1 = s1 + st[4 * m + 1];
-    s2 = s2 + st[4 * m + 2];
-    s3 = s3 + st[4 * m + 3];
-  }
-  const double oon = 1.0 / (double)km;
-  const double sm[2] = {s0 * oon, s1 * oon};
-  const double dm[2] = {s2 * oon, s3 * oon};
-  const bool lazy = (km + 4) < 20;
-  const double z0 = lazy ? -0.0 : 0.0;
-  double c0 = z0, c1 = z0, c2 = z0, c3 = z0;
-  for (int m = 0; m < km; ++m) {
-    const double e0 = st[4 * m] - sm[0], e1 = st[4 * m + 1] - sm[1];
-    double d0 = st[4 * m + 2] - dm[0], d1 = st[4 * m + 3] - dm[1];
-    if (lazy) {
-      d0 = oon * d0;
-      d1 = oon * d1;
-    }
-    c0 = c0 + d0 * e0;
-    c1 = c1 + d0 * e1;
-    c2 = c2 + d1 * e0;
-    c3 = c3 + d1 * e1;
-  }
-  if (!lazy) {
-    c0 = c0 * oon; c1 = c1 * oon; c2 = c2 * oon; c3 = c3 * oon;
-  }
-  const double Sg[4] = {c0, c2, c1, c3};
-  double R[4], t[2], g;
-  umeyama_finish(Sg, sm, dm, R, t, &g);  // a non-finite member: (R, t) = NaN
-  const double o[6] = {R[0], R[1], R[2], R[3], t[0], t[1]};
+  double o[6];
+  own_row_align<SL>(adjrow, i, pf, qs, u, n, lane, st, o);
   if (lane == 0) {
     double* od = P.Rt + (size_t)k * 6;
     od[0] = o[0]; od[1] = o[1]; od[2] = o[2]; od[3] = o[3]; od[4] = o[4]; od[5] = o[5];

@@ -445,6 +445,137 @@ def vehicle_start(table, fidx, vehid, q, Pt, qidx=None, want_bid=True, stream=No
     return out
 
 
+class FleetAuction:
+    """acl_fleet_auction_batch (added within ABI 11): the message-level CBAA of
+    B swarms of n vehicles -- every vehicle an Auctioneer of the reference
+    with its receive queue and START / current / next buckets -- advanced tick
+    by tick on the device, one launch per run() (auctioneer.cpp:66-306,
+    419-465; include/aclswarm_amd.h states the model and its limits: a tick is
+    1 ms of auctioneer time, message latency below one tick, per-sender FIFO,
+    queue_cap bids per queue, n <= 128).
+
+    fidx [B] i32 on the table's device; Pt [B][n][n] int16 (uint16 bits):
+    vehicle v's own row, formation point -> vehicle (None: identity rows);
+    queue_cap None: 4 n; max_iter 0: 2 n. The object owns the state tensors
+    (Pt, open, invalid, just_received, biditer, price, who, Rt), the outputs
+    (final_price, final_who, done_tick, vflags, n_thrown, n_tally, queue_len)
+    and the workspace. just_received starts at 1 (a formation just set); the
+    caller may rewrite any state tensor between runs. Raises ValueError on a
+    malformed argument before anything runs."""
+
+    def __init__(self, table, fidx, Pt=None, queue_cap=None, max_iter=0):
+        n = table.n
+        if n < 1 or n > L.FLEET_MAX_N:
+            raise ValueError(f"FleetAuction: n = {n} out of range [1, {L.FLEET_MAX_N}]")
+        if not isinstance(fidx, torch.Tensor) or fidx.dim() != 1:
+            raise ValueError("FleetAuction: fidx must be a torch tensor of shape (B,)")
+        B = int(fidx.shape[0])
+        dev = table.p.device
+        want = {"fidx": (fidx, (torch.int32,), (B,))}
+        if Pt is not None:
+            want["Pt"] = (Pt, (torch.int16, torch.uint16), (B, n, n))
+        self._check("FleetAuction", want, dev)
+        if B < 1:
+            raise ValueError("FleetAuction: fidx is empty")
+        if queue_cap is None:
+            queue_cap = 4 * n
+        if int(queue_cap) < 1:
+            raise ValueError(f"FleetAuction: queue_cap = {queue_cap} < 1")
+        if int(max_iter) < 0:
+            raise ValueError(f"FleetAuction: max_iter = {max_iter} < 0")
+        self.table, self.fidx, self.n, self.B, self.device = table, fidx, n, B, dev
+        self.queue_cap, self.max_iter = int(queue_cap), int(max_iter)
+        if Pt is None:
+            Pt = torch.arange(n, dtype=torch.int16, device=dev).repeat(B, n, 1)
+        self.Pt = Pt.clone().contiguous()
+
+        def z(shape, dt, fill=0):
+            return torch.full(shape, fill, dtype=dt, device=dev)
+        self.open = z((B, n), torch.uint8)
+        self.invalid = z((B, n), torch.uint8)
+        self.just_received = z((B, n), torch.uint8, 1)
+        self.biditer = z((B, n), torch.int32)
+        self.price = z((B, n, n), torch.float32)
+        self.who = z((B, n, n), torch.int32, -1)
+        self.Rt = z((B, n, 6), torch.float64)
+        self.final_price = z((B, n, n), torch.float32)
+        self.final_who = z((B, n, n), torch.int32, -1)
+        self.done_tick = z((B, n), torch.int32, -1)
+        self.vflags = z((B, n), torch.int32)
+        self.n_thrown = z((B, n), torch.int32)
+        self.n_tally = z((B, n), torch.int32)
+        self.queue_len = z((B, n), torch.int32)
+        self._status = z((B, 4), torch.int32)
+        self.ws = None  # allocated (zero-filled) by the first run
+
+    @staticmethod
+    def _check(what, want, dev):
+        for name, (t, dts, shape) in want.items():
+            if not isinstance(t, torch.Tensor) or t.dtype not in dts or \
+                    tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"{what}: {name} must be a contiguous {dts[0]} tensor of shape "
+                                 f"{shape} on {dev}")
+
+    def workspace_bytes(self):
+        return int(L.lib().acl_fleet_workspace_bytes(self.n, self.B, self.queue_cap))
+
+    def run(self, ticks, q=None, cmd=None, history=False, stream=None):
+        """Apply the commands cmd [B][n] u8 (FLEET_NONE / FLEET_START /
+        FLEET_FLUSH of _lib; None: carry on) with the snapshot q [B][n][3]
+        f64 that START reads, then run up to `ticks` ticks (each swarm stops
+        at its quiescence). With history=True returns {"biditer": [ticks][B]
+        [n] i32, "open": [ticks][B][n] u8} device tensors, else None."""
+        B, n, dev = self.B, self.n, self.device
+        ticks = int(ticks)
+        if ticks < 0:
+            raise ValueError(f"FleetAuction.run: ticks = {ticks} < 0")
+        want = {}
+        if q is not None:
+            want["q"] = (q, (torch.float64,), (B, n, 3))
+        if cmd is not None:
+            want["cmd"] = (cmd, (torch.uint8,), (B, n))
+        self._check("FleetAuction.run", want, dev)
+        if cmd is not None and q is None:
+            raise ValueError("FleetAuction.run: cmd is given without the snapshot q")
+        if cmd is not None and ticks < 1:
+            raise ValueError("FleetAuction.run: a run with cmd must run at least one tick")
+        if dev.type != "cuda":
+            raise ValueError(f"FleetAuction.run: the tensors must be on a CUDA device, not {dev}")
+        if self.ws is None:
+            self.ws = torch.zeros(self.workspace_bytes(), dtype=torch.uint8, device=dev)
+        hist = None
+        if history:
+            hist = {"biditer": torch.empty((ticks, B, n), dtype=torch.int32, device=dev),
+                    "open": torch.empty((ticks, B, n), dtype=torch.uint8, device=dev)}
+        a = L.FleetAuctionArgs()
+        a.B, a.ticks, a.max_iter, a.queue_cap = B, ticks, self.max_iter, self.queue_cap
+        a.fidx = self.fidx.data_ptr()
+        a.q = q.data_ptr() if q is not None else None
+        a.cmd = cmd.data_ptr() if cmd is not None else None
+        for k in ("Pt", "open", "invalid", "just_received", "biditer", "price", "who", "Rt",
+                  "final_price", "final_who", "done_tick", "vflags", "n_thrown", "n_tally",
+                  "queue_len"):
+            setattr(a, k, getattr(self, k).data_ptr())
+        a.status = self._status.data_ptr()
+        if hist is not None:
+            a.hist_biditer = hist["biditer"].data_ptr()
+            a.hist_open = hist["open"].data_ptr()
+        a.workspace = self.ws.data_ptr()
+        a.workspace_bytes = self.ws.numel()
+        F = self.table.struct()
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        L.check(L.lib().acl_fleet_auction_batch(ct.byref(F), ct.byref(a), ct.c_void_p(stream)),
+                "acl_fleet_auction_batch")
+        return hist
+
+    def status(self):
+        """The last run's acl_fleet_status_t records as a structured numpy
+        array [B] (ticks_run, n_open, n_queued, flags); synchronises."""
+        arr = np.ascontiguousarray(self._status.cpu().numpy())
+        return arr.view(L.FLEET_STATUS_DTYPE).reshape(-1)
+
+
 def write_assignment_log(path, q, adj, lastP, p, align_Rt, P):
     """Auctioneer::logAssignment's binary record (auctioneer.cpp:577-597),
     host arrays: q, p [n][3]; adj [n][n] (adj[i][j] = adjmat(i,j)); lastP, P

@@ -555,6 +555,120 @@ typedef struct {
 acl_status_t acl_vehicle_start_batch(const acl_formations_t* formations,
                                      const acl_vehicle_start_args_t* args, void* stream);
 
+/* ---- message-level CBAA for whole fleets (added within ABI 11) -------------
+ * B swarms of n vehicles, each vehicle an Auctioneer of the reference with
+ * its receive queue and its START / current / next buckets, advanced tick by
+ * tick on the device in one launch (one workgroup per swarm). An added
+ * symbol: ACL_ABI_VERSION stays 11 (no existing struct or call changed).
+ *
+ * One tick is one Auctioneer::tick() of every vehicle (auctioneer_dt = 1 ms,
+ * coordination.launch:23). Vehicle w receives sender u's bids exactly when u
+ * is a neighbour of w under w's OWN row at the moment of delivery: with i
+ * the point of w (Pt[w][i] == w), some j has adj(i, j) and Pt[w][j] == u
+ * (connectToNeighbors, coordination_ros.cpp:392-428). A vehicle whose row is
+ * not a permutation of 0..n-1 receives nothing.
+ *
+ * A call first applies the commands cmd[b][v] (NULL: none):
+ *   ACL_FLEET_NONE   nothing (any value not listed here is ignored);
+ *   ACL_FLEET_FLUSH  Auctioneer::flush (auctioneer.cpp:66-74): reset(), the
+ *                    START bucket and the queue cleared, invalid = 0;
+ *   ACL_FLEET_START  Auctioneer::start (:78-120) from snapshot q[b]: reset(),
+ *                    the current bucket takes the START bucket (then cleared),
+ *                    Rt[b][v] = the alignment under the vehicle's own row (the
+ *                    bits of acl_vehicle_start_batch), the START bid, open = 1,
+ *                    the bid published with iter 0. A row that is not a
+ *                    permutation starts nothing: reset() only, the vehicle
+ *                    stays closed, publishes nothing, ACL_FLEET_V_BAD_ROW.
+ * Bids a vehicle had published and that were not yet delivered stay in
+ * flight through a command.
+ * Then `ticks` ticks, each in two phases:
+ *   1. delivery: every bid published since the previous delivery, in
+ *      ascending sender id (a sender's own bids in the order it published
+ *      them), is appended to the queue of every subscriber, open or closed.
+ *      A bid that finds the queue holding queue_cap bids is dropped
+ *      (ACL_FLEET_V_OVERFLOW, ACL_FLEET_OVERFLOW). Message latency is
+ *      therefore below one tick, and each sender's bids arrive in order.
+ *   2. processing: every open vehicle with a queued bid pops one and runs
+ *      processBid (:182-306): iter 0 -> the START bucket; iter == biditer ->
+ *      current, else iter == biditer + 1 -> next, else thrown away
+ *      (n_thrown); the first entry of a sender in a bucket stays. When the
+ *      current bucket holds every subscribed sender, the tally of
+ *      acl_cbaa_step_batch over the current bucket and the vehicle's own bid
+ *      (ascending vehid) runs, ++biditer, current = next, next cleared, the
+ *      START bucket cleared when biditer == 1. At biditer >= max_iter the
+ *      table goes to final_price / final_who; a valid table (a permutation)
+ *      is adopted into Pt[b][v] when just_received is set or it differs
+ *      (shouldUseAssignment, :310-321; just_received is cleared), an invalid
+ *      one sets invalid; then reset(): the vehicle closes and its queue
+ *      stays. Otherwise the bid is published with the new biditer.
+ * A swarm is quiescent when nothing is in flight and no open vehicle has a
+ * queued bid; its loop stops there (ticks_run counts the ticks run). A call
+ * with cmd == NULL carries on from the stored state: ticks = a then b equals
+ * a + b. A call with cmd != NULL must run at least one tick.
+ *
+ * The per-swarm state that is not in the arrays below (queues, buckets, bids
+ * in flight, each vehicle's start position, the tick counter) lives in the
+ * caller's workspace, acl_fleet_workspace_bytes(n, B, queue_cap) bytes that
+ * the caller zero-fills once and hands back unchanged with the same n, B and
+ * queue_cap. A zero-filled workspace and zeroed state arrays are freshly
+ * constructed auctioneers (the caller writes the identity rows and sets
+ * just_received). n in [1, 128]. Stream-ordered, never synchronises. */
+#define ACL_FLEET_NONE  0
+#define ACL_FLEET_START 1
+#define ACL_FLEET_FLUSH 2
+
+#define ACL_FLEET_QUIESCENT 0x1 /* status.flags: as the call returns */
+#define ACL_FLEET_OVERFLOW  0x2 /* a bid was dropped in this call */
+#define ACL_FLEET_BAD_INPUT 0x4 /* fidx out of range: the swarm is untouched */
+
+#define ACL_FLEET_V_STARTED   0x01
+#define ACL_FLEET_V_BAD_ROW   0x02
+#define ACL_FLEET_V_CONSENSUS 0x04
+#define ACL_FLEET_V_ADOPTED   0x08
+#define ACL_FLEET_V_INVALID   0x10
+#define ACL_FLEET_V_OVERFLOW  0x20
+
+typedef struct {
+  int32_t ticks_run; /* ticks run in this call */
+  int32_t n_open;    /* open vehicles as the call returns */
+  int32_t n_queued;  /* queued bids over all vehicles as the call returns */
+  int32_t flags;     /* ACL_FLEET_* */
+} acl_fleet_status_t; /* 16 bytes */
+
+typedef struct {
+  int32_t B;              /* swarms */
+  int32_t ticks;          /* >= 0; >= 1 with cmd */
+  int32_t max_iter;       /* consensus at biditer >= max_iter; 0: 2n */
+  int32_t queue_cap;      /* >= 1: bids a vehicle's queue holds */
+  const int32_t* fidx;    /* [B] */
+  const double* q;        /* [B][n][3] read only by START (NULL allowed with cmd == NULL) */
+  const uint8_t* cmd;     /* [B][n] ACL_FLEET_NONE / START / FLUSH, or NULL */
+  uint16_t* Pt;           /* [B][n][n] in/out: vehicle v's own row, formation point -> vehicle */
+  uint8_t* open;          /* [B][n] in/out auction_is_open_ */
+  uint8_t* invalid;       /* [B][n] in/out invalid_assignment_ */
+  uint8_t* just_received; /* [B][n] in/out formation_just_received_ */
+  int32_t* biditer;       /* [B][n] in/out */
+  float* price;           /* [B][n][n] in/out bid_ */
+  int32_t* who;           /* [B][n][n] in/out */
+  double* Rt;             /* [B][n][6] in/out: written by START */
+  float* final_price;     /* [B][n][n] out at a vehicle's consensus, else left */
+  int32_t* final_who;     /* [B][n][n] */
+  int32_t* done_tick;     /* [B][n] out: absolute tick (from 0) of this call's consensus */
+  int32_t* vflags;        /* [B][n] in/out: ACL_FLEET_V_* ORed in */
+  int32_t* n_thrown;      /* [B][n] in/out: accumulated */
+  int32_t* n_tally;       /* [B][n] in/out: accumulated */
+  int32_t* queue_len;     /* [B][n] out */
+  acl_fleet_status_t* status; /* [B] out */
+  int32_t* hist_biditer;  /* [ticks][B][n] out or NULL; rows past quiescence repeat the last */
+  uint8_t* hist_open;     /* [ticks][B][n] out or NULL */
+  void* workspace;
+  size_t workspace_bytes;
+} acl_fleet_auction_args_t;
+
+size_t acl_fleet_workspace_bytes(int32_t n, int32_t B, int32_t queue_cap);
+acl_status_t acl_fleet_auction_batch(const acl_formations_t* formations,
+                                     const acl_fleet_auction_args_t* args, void* stream);
+
 /* ---- closed-loop batched episodes ---------------------
  * B swarms flown for `steps` control periods in lockstep: the discrete-time
  * model of one vehicle's node graph (CoordinationROS + Safety) with a

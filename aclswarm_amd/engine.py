@@ -611,6 +611,30 @@ def read_assignment_log(path):
     return r
 
 
+def _check_state(what, table, want):
+    """The argument checks of Episode and Trial, before anything is allocated
+    or the library is called: want maps a name to (tensor, dtype, shape), the
+    first entry q; a None in a shape stands for any K >= 1. Everything must be
+    a contiguous torch tensor of that dtype and shape on q's device, which is
+    the formation table's and a CUDA one."""
+    for name, (t, dt, shape) in want.items():
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{what}: {name} must be a torch tensor")
+    dev = next(iter(want.values()))[0].device
+    for name, (t, dt, shape) in want.items():
+        ok = t.dtype == dt and t.dim() == len(shape) and \
+            all(d >= 1 if s is None else s == d for s, d in zip(shape, t.shape))
+        if not ok or not t.is_contiguous() or t.device != dev:
+            dims = "".join(f"[{'K >= 1' if s is None else s}]" for s in shape)
+            raise ValueError(f"{what}: {name} must be a contiguous {dt} tensor of shape {dims} "
+                             f"on {dev}")
+    if table.p.device != dev:
+        raise ValueError(f"{what}: the formation table is on {table.p.device}, the swarms on "
+                         f"{dev}")
+    if dev.type != "cuda":
+        raise ValueError(f"{what}: the tensors must be on a CUDA device, not {dev}")
+
+
 class Episode:
     """Closed-loop batched episodes (acl_episode_batch):
     the per-swarm state that persists across calls -- positions, velocities,
@@ -619,16 +643,25 @@ class Episode:
 
     fidx [B] int32, q/vel [B][n][3] f64, P [B][n] int16 (uint16 bits), all on
     the device; they are copied, the caller's tensors are not modified.
+    Raises ValueError on a malformed argument before anything runs.
     """
 
     def __init__(self, table, fidx, q, vel, P, params=None, cntrl=None, safety=None):
+        n = table.n
+        if not isinstance(q, torch.Tensor) or q.dim() != 3:
+            raise ValueError(f"Episode: q must be a torch.float64 tensor of shape [B][{n}][3]")
+        B = int(q.shape[0])
+        _check_state("Episode", table, {"q": (q, torch.float64, (B, n, 3)),
+                                        "vel": (vel, torch.float64, (B, n, 3)),
+                                        "fidx": (fidx, torch.int32, (B,)),
+                                        "P": (P, torch.int16, (B, n))})
         dev = q.device
         self.table = table
-        self.B, self.n = int(q.shape[0]), table.n
+        self.B, self.n = B, n
         self.ep = params or L.default_episode_params()
         self.cntrl = cntrl or L.default_gains()
         self.safety = safety or L.default_safety()
-        self.fidx = fidx.contiguous()
+        self.fidx = fidx
         self.q = q.clone().contiguous()
         self.vel = vel.clone().contiguous()
         self.P = P.clone().contiguous()
@@ -692,21 +725,27 @@ class Trial:
     across calls (a trial can be run in chunks of steps).
 
     fseq [B][K] int32, q/vel [B][n][3] f64 on the device (copied). The
-    assignment starts at identity (no formation yet)."""
+    assignment starts at identity (no formation yet). Raises ValueError on a
+    malformed argument before anything runs."""
 
     def __init__(self, table, fseq, q, vel, params=None, cntrl=None, safety=None):
+        n = table.n
+        if not isinstance(q, torch.Tensor) or q.dim() != 3:
+            raise ValueError(f"Trial: q must be a torch.float64 tensor of shape [B][{n}][3]")
+        B = int(q.shape[0])
+        _check_state("Trial", table, {"q": (q, torch.float64, (B, n, 3)),
+                                      "vel": (vel, torch.float64, (B, n, 3)),
+                                      "fseq": (fseq, torch.int32, (B, None))})
         dev = q.device
         self.table = table
-        self.B, self.n = int(q.shape[0]), table.n
+        self.B, self.n = B, n
         self.K = int(fseq.shape[1])
         self.tp = params or L.default_trial_params()
         self.cntrl = cntrl or L.default_gains()
         self.safety = safety or L.default_safety()
         B, n, K = self.B, self.n, self.K
         Lb = int(self.tp.ep.bufflen)
-        self.fseq = fseq.to(torch.int32).contiguous()
-        if tuple(self.fseq.shape) != (B, K):
-            raise ValueError("Trial: fseq must be [B][K]")
+        self.fseq = fseq
         self.fidx = torch.empty(B, dtype=torch.int32, device=dev)
         self.q = q.clone().contiguous()
         self.vel = vel.clone().contiguous()

@@ -251,6 +251,64 @@ def test_episode_defaults_and_argument_errors_without_gpu():
     assert math.isfinite(e.control_dt)
 
 
+def test_engine_episode_validates_before_anything_runs(monkeypatch):
+    """Each malformed argument of engine.Episode raises ValueError before the
+    library is loaded or anything is allocated (host and meta tensors: no
+    device is touched)."""
+    import torch
+    from aclswarm_amd import _lib as L
+    from aclswarm_amd import engine
+    pts, adj, gains, _ = H.swarm6()
+    Tc = engine.FormationTable.from_host(pts, adj, gains, device="cpu")
+    Tm = engine.FormationTable.from_host(pts, adj, gains, device="meta")
+
+    def no_lib():
+        raise AssertionError("Episode loaded the library")
+    monkeypatch.setattr(L, "lib", no_lib)
+    n, B = Tc.n, 4
+    meta = torch.device("meta")
+
+    def good(dev="cpu"):
+        return dict(fidx=torch.zeros(B, dtype=torch.int32, device=dev),
+                    q=torch.zeros((B, n, 3), dtype=torch.float64, device=dev),
+                    vel=torch.zeros((B, n, 3), dtype=torch.float64, device=dev),
+                    P=torch.zeros((B, n), dtype=torch.int16, device=dev))
+    g = good()
+    bad = [
+        ("fidx", g["fidx"].to(torch.int64)),                          # dtype
+        ("q", g["q"].to(torch.float32)),
+        ("vel", g["vel"].to(torch.float32)),
+        ("P", g["P"].to(torch.int32)),
+        ("fidx", torch.zeros((B, 1), dtype=torch.int32)),             # shape
+        ("fidx", torch.zeros(B + 1, dtype=torch.int32)),
+        ("q", torch.zeros((B, n + 1, 3), dtype=torch.float64)),       # n is the table's
+        ("q", torch.zeros((B, n), dtype=torch.float64)),
+        ("vel", torch.zeros((B + 1, n, 3), dtype=torch.float64)),
+        ("P", torch.zeros((B, n + 1), dtype=torch.int16)),
+        ("P", torch.zeros((n, B), dtype=torch.int16).t()),            # not contiguous
+        ("q", torch.zeros((B, 3, n), dtype=torch.float64).transpose(1, 2)),
+        ("fidx", torch.zeros(2 * B, dtype=torch.int32)[::2]),
+        ("fidx", torch.zeros(B, dtype=torch.int32, device=meta)),     # mixed devices
+        ("vel", torch.zeros((B, n, 3), dtype=torch.float64, device=meta)),
+        ("P", torch.zeros((B, n), dtype=torch.int16, device=meta)),
+        ("fidx", np.zeros(B, np.int32)),                              # not tensors
+        ("q", np.zeros((B, n, 3))),
+        ("P", None),
+    ]
+    for name, t in bad:
+        kw = dict(g)
+        kw[name] = t
+        with pytest.raises(ValueError, match="Episode: " + name):
+            engine.Episode(Tc, **kw)
+    with pytest.raises(ValueError, match="formation table"):
+        engine.Episode(Tm, **g)
+    # consistent tensors that are not on a CUDA device
+    with pytest.raises(ValueError, match="CUDA"):
+        engine.Episode(Tc, **g)
+    with pytest.raises(ValueError, match="CUDA"):
+        engine.Episode(Tm, **good(meta))
+
+
 def test_formation_generator_argument_errors_without_gpu():
     from aclswarm_amd import _lib as L
     lib = L.lib()

@@ -13,22 +13,20 @@ per-trial records -- the CSV row of complete() (supervisor.py:404-415): the
 smoothed planar distance per vehicle, time to converge, gridlock time and
 assignments per formation -- and the counters, bit for bit.
 """
+import functools
+
 import numpy as np
 import pytest
 
 import helpers as H
+import trial_cases as C
 import trial_oracle as T
+from trial_cases import FAST, FAST_EP
 
 pytestmark = pytest.mark.gpu
 
 U_RTOL = 1e-5
 Q_ATOL = 1e-9
-
-# short supervisor timings so that the CPU restatement stays fast: the state
-# machine is the reference's, the clocks are scaled down
-FAST = dict(settle_steps=10, hover_wait=0.2, formation_received_wait=0.1, converged_wait=0.2,
-            gridlock_timeout=2.0, trial_timeout=60.0, assignment_timeout=2.0)
-FAST_EP = dict(auction_every=20, bufflen=10)
 
 
 def _swarm6_case(B=4, seed=3, central=False, **tp):
@@ -41,16 +39,18 @@ def _swarm6_case(B=4, seed=3, central=False, **tp):
                 tp=dict(FAST, **tp), ep=dict(FAST_EP, assignment=1 if central else 0))
 
 
-def _chain_case(n=10, B=3, seed=21):
+def _chain_case(n=10, B=3, seed=21, tail=None, trial_timeout=8.0):
     """Chain formations whose first auctions end with vehicles on different
     tables: some controllers start before others (per-vehicle
-    first_assignment_), the flush rule fires."""
+    first_assignment_), the flush rule fires. tail: lollipops instead (a
+    clique with a chain of `tail` vehicles), as the episodes' n = 100 and
+    n = 136 cases."""
     import test_gpu_episode as GE
-    c = GE._chain_case(n, 2 * B, seed)
+    c = GE._chain_case(n, 2 * B, seed, tail=tail)
     # swarm b starts on formation b (its start disagrees there), then B + b
     fseq = np.stack([np.arange(B), B + np.arange(B)], axis=1).astype(np.int32)
     return dict(pts=c["pts"], adj=c["adj"], gains=c["gains"], q=c["q"][:B], vel=c["vel"][:B],
-                fseq=fseq, tp=dict(FAST, trial_timeout=8.0), ep=dict(FAST_EP))
+                fseq=fseq, tp=dict(FAST, trial_timeout=trial_timeout), ep=dict(FAST_EP))
 
 
 def _run(case, dev, steps, chunks=None):
@@ -155,6 +155,107 @@ def test_trial_teacher_forced_disagreeing_chain(cuda):
     assert partial
 
 
+# -- above one wave: tests/trial_cases.py -------------------------------------
+
+# the step at which the slowest of calm, late_last and pair_last ends on the
+# CPU restatement (late_last: 230 at n = 65, 236 at n = 129), and 5 ticks
+TWO_WAVES_STEPS = {65: 240, 129: 246}
+
+
+@functools.lru_cache(maxsize=None)
+def _two_waves_case(n):
+    return C.batch([C.calm(n), C.late_last(n), C.pair_last(n), C.reassign(n)])
+
+
+def _window_means(h, b, step, tp):
+    """The per-vehicle mean of |u| over the bufflen ticks that end at `step`,
+    from the recorded commands."""
+    L, every = tp["ep"]["bufflen"], tp["ep"]["sample_every"]
+    u = h["u"][step - every * (L - 1):step + 1:every, b]
+    assert u.shape[0] == L
+    return np.sqrt((u * u).sum(axis=2)).mean(axis=0)
+
+
+@pytest.mark.parametrize("n", [65, 129])
+def test_trial_teacher_forced_two_waves(cuda, n):
+    """calm, late_last, pair_last and reassign in one batch. n = 65: the
+    smallest n with a second wave of the 128-thread kernels (one live lane);
+    n = 129: the smallest with a second pass of their vehicle loops (one live
+    lane), and the smallest on the wide auction and the 1 024-thread control
+    path. The single-formation cases fly their formation twice (K = 2 is
+    reassign's). After the parity, the GPU's own run must have gone through
+    what each case is for."""
+    steps = TWO_WAVES_STEPS[n]
+    case = _two_waves_case(n)
+    a, b, c, d = range(4)
+    tr, h, tp = _run(case, cuda, steps)
+    fin = _teacher_forced(case, tr, h, tp, steps)
+    st = tr.status()
+    assert fin[a]["state"] == T.COMPLETE and fin[b]["state"] == T.COMPLETE
+    assert st[a]["state"] == T.COMPLETE and st[b]["state"] == T.COMPLETE
+    assert (st[c]["state"], st[c]["last_state"]) == (T.TERMINATE, T.GRIDLOCK)
+    # the last vehicle alone holds late_last out of IN_FORMATION for a window
+    in_a, in_b = (C.first_step(h["state"][:, x], T.IN_FORMATION) for x in (a, b))
+    L = tp["ep"]["bufflen"]
+    assert in_a > 0 and in_b >= in_a + 2 * L, (in_a, in_b)
+    assert h["state"][in_a, b] == T.FLYING
+    assert C.first_step(h["state"][:, b], T.FLYING) == C.first_step(h["state"][:, a], T.FLYING)
+    m = _window_means(h, b, in_a, tp)
+    thr = tp["ep"]["orig_zero_vel_thr"]
+    print(f"n {n}: IN_FORMATION calm {in_a} late_last {in_b}; late_last window means at "
+          f"{in_a}: others max {m[:n - 1].max():.4f}, vehicle n-1 {m[n - 1]:.4f}")
+    assert (m[:n - 1] < thr).all() and m[n - 1] >= thr
+    # the last two vehicles alone hold pair_last's collision avoidance
+    assert not h["ca"][:, c, :n - 2].any()
+    assert h["ca"][:, c, n - 2].any() and h["ca"][:, c, n - 1].any()
+    # reassign: vehicle 0's message after a changed table was counted
+    rec = tr.records()
+    assert rec["assignments"][d].max() >= 2, rec["assignments"][d]
+
+
+def test_trial_teacher_forced_central_two_waves(cuda):
+    """calm and two_formations at n = 65 under the operator's Hungarian."""
+    steps = 390     # two_formations COMPLETE at 378 on the CPU restatement
+    n = 65
+    case = C.batch([C.calm(n), C.two_formations(n)], assignment=1)
+    tr, h, tp = _run(case, cuda, steps)
+    fin = _teacher_forced(case, tr, h, tp, steps)
+    for r in fin:
+        assert r["state"] == T.COMPLETE and r["done_step"] >= 0
+        assert all(x > 0 for x in r["time"]) and r["assignments"] == [1, 1]
+    assert (tr.status()["state"] == T.COMPLETE).all()
+
+
+@pytest.mark.parametrize("n, seed, tail", [(100, 23, 40), (136, 25, 60)])
+def test_trial_teacher_forced_lollipop(cuda, n, seed, tail):
+    """Per-vehicle adoption at the trial bench's size and on the wide path:
+    the lollipops of the episodes' n = 100 and n = 136 cases, two trials of
+    two formations; the watchdog ends them after 61 ticks."""
+    steps = 126
+    case = _chain_case(n, 2, seed, tail=tail, trial_timeout=1.2)
+    tr, h, tp = _run(case, cuda, steps)
+    _teacher_forced(case, tr, h, tp, steps)
+    st = tr.status()
+    assert int(st["n_disagree"].sum()) > 0
+    partial = ((h["ctl"].sum(axis=2) > 0) & (h["ctl"].sum(axis=2) < n)).any()
+    assert partial
+
+
+def test_trial_first_auction_n257(cuda):
+    """calm at n = 257 through the commit, the first agreed auction and the
+    WAITING -> FLYING tick: the smallest n with a second pass of the adopt
+    kernel's 256-thread loops (and a fifth of the commit's 64-thread one)."""
+    steps = 36      # FLYING at 32 on the CPU restatement
+    n = 257
+    case = C.batch([C.calm(n, seed=0), C.calm(n, seed=1)])
+    tr, h, tp = _run(case, cuda, steps)
+    _teacher_forced(case, tr, h, tp, steps)
+    st = tr.status()
+    assert (st["state"] == T.FLYING).all() and (st["n_auctions"] >= 1).all()
+    assert h["ctl"][-1].all()
+    assert (tr.records()["assignments"][:, 0] == 1).all()
+
+
 @pytest.mark.parametrize("what", ["assignment", "watchdog", "gridlock"])
 def test_trial_terminations(cuda, what):
     """The three ways supervisor.py terminates a trial: no assignment within
@@ -178,11 +279,15 @@ def test_trial_terminations(cuda, what):
         assert last == want, last
 
 
-def test_trial_chunks_equal_one_call(cuda):
+@pytest.mark.parametrize("which", ["swarm6", "two_waves129"])
+def test_trial_chunks_equal_one_call(cuda, which):
     import torch
-    case = _swarm6_case(B=3)
-    tr1, h1, _ = _run(case, cuda, 500)
-    tr2, h2, _ = _run(case, cuda, 500, chunks=[137, 200, 163])
+    if which == "swarm6":
+        case, steps, chunks = _swarm6_case(B=3), 500, [137, 200, 163]
+    else:
+        case, steps, chunks = _two_waves_case(129), TWO_WAVES_STEPS[129], [97, 100, 49]
+    tr1, h1, _ = _run(case, cuda, steps)
+    tr2, h2, _ = _run(case, cuda, steps, chunks=chunks)
     for k in ("q", "vel", "P", "ctl", "state"):
         assert np.array_equal(h1[k], h2[k]), k
     for k in ("q", "vel", "P", "flush", "ts", "ctl_on", "ring_u", "ring_ca", "posf", "dist",

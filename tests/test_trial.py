@@ -1,14 +1,18 @@
 """CPU suite for batched Monte-Carlo trials (acl_trial_batch):
 the supervisor restatement (oracle/trial_oracle.py) on scripted signals
-against supervisor.py's rules, a whole CPU trial on swarm6_3d, and the trial
-ABI (struct layout, defaults, argument errors) without a GPU."""
+against supervisor.py's rules, a whole CPU trial on swarm6_3d, the cases of
+the GPU parity tests above one wave (tests/trial_cases.py: their gains, and
+that each still reaches the edge it is for), engine.Trial's argument checks,
+and the trial ABI (struct layout, defaults, argument errors) without a GPU."""
 import ctypes as ct
 import os
 import subprocess
 
 import numpy as np
+import pytest
 
 import helpers as H
+import trial_cases as C
 import trial_oracle as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -85,6 +89,158 @@ def test_cpu_trial_swarm6_runs_to_an_end():
     assert t.done and t.sup.state in (T.COMPLETE, T.TERMINATE)
     assert np.isfinite(qf).all()
     assert t.counts["auctions"] > 0
+
+
+# -- the cases of the GPU parity tests above one wave (tests/trial_cases.py) --
+
+@pytest.mark.parametrize("n", [5, 65])
+def test_closed_form_gains(n):
+    """Zero row sums, the formation in the kernel, the reference's block
+    structure [a b 0; -b a 0; 0 0 c] on every edge (and on the diagonal)."""
+    p, _ = C.formation_points(n)
+    G = C.closed_form_gains(p)
+    assert G.shape == (3 * n, 3 * n)
+    assert np.abs(G.reshape(3 * n, n, 3).sum(axis=1)).max() < 1e-12
+    assert np.abs(G @ p.ravel()).max() < 1e-10
+    Gb = G.reshape(n, 3, n, 3).transpose(0, 2, 1, 3)       # [i][j] 3 x 3
+    assert (Gb[..., 0, 0] == Gb[..., 1, 1]).all() and (Gb[..., 0, 1] == -Gb[..., 1, 0]).all()
+    assert (Gb[..., :2, 2] == 0).all() and (Gb[..., 2, :2] == 0).all()
+    off = ~np.eye(n, dtype=bool)
+    assert (np.abs(Gb[off][:, 0, 0]) > 0).any() and (np.abs(Gb[off][:, 0, 1]) > 0).any()
+    assert (np.abs(Gb[off][:, 2, 2]) > 0).any()
+    # the kernel also holds the formation turned and scaled in xy: what the
+    # swarm flies into
+    z = (p[:, 0] + 1j * p[:, 1]) * (0.7 - 0.4j)
+    pr = np.c_[z.real, z.imag, 2.0 * p[:, 2] + 1.0]
+    assert np.abs(G @ pr.ravel()).max() < 1e-10
+    # negative semidefinite: the flight is stable
+    assert np.linalg.eigvalsh(0.5 * (G + G.T)).max() < 1e-12
+
+
+def _fly(case, steps):
+    """One case alone on the CPU restatement, with the batch's parameters;
+    per-step states, CA flags, commands and the assignment counts."""
+    tp = C.oracle_params(case)
+    forms = list(zip(case["pts"], case["adj"], case["gains"]))
+    out = []
+    for b in range(case["q"].shape[0]):
+        t = T.TrialSwarm(case["q"].shape[1], case["fseq"][b], forms, tp)
+        q, vel = case["q"][b].copy(), case["vel"][b].copy()
+        states, us, cas, rise = [], [], [], -1
+        for k in range(steps):
+            q, vel, u, ca = t.step(k, q, vel)
+            states.append(t.sup.state); us.append(u); cas.append(ca)
+            if rise < 0 and max(t.sup.assignments) >= 2:
+                rise = k
+            if t.done:
+                break
+        out.append(dict(t=t, states=np.array(states), u=np.array(us), ca=np.array(cas),
+                        rise=rise))
+    return out, tp
+
+
+def _check_cases_on_cpu(n, steps, steps_e):
+    case = C.batch([C.calm(n), C.late_last(n), C.pair_last(n), C.reassign(n)])
+    (a, b, c, d), tp = _fly(case, steps)
+    L, every = tp["ep"]["bufflen"], tp["ep"]["sample_every"]
+    for x in (a, b):
+        assert x["t"].sup.state == T.COMPLETE and x["t"].done
+        assert not x["ca"].any() and (x["t"].state.P == np.arange(n)).all()
+    # late_last: the last vehicle alone vetoes has_converged for a window
+    in_a, in_b = (C.first_step(x["states"], T.IN_FORMATION) for x in (a, b))
+    assert in_a > 0 and in_b >= in_a + 2 * L, (in_a, in_b)
+    assert b["states"][in_a] == T.FLYING
+    u = b["u"][in_a - every * (L - 1):in_a + 1:every]
+    m = np.sqrt((u * u).sum(axis=2)).mean(axis=0)
+    thr = tp["ep"]["orig_zero_vel_thr"]
+    assert (m[:n - 1] < thr).all() and m[n - 1] >= thr, (m[:n - 1].max(), m[n - 1])
+    # pair_last: the last two vehicles alone hold the collision avoidance
+    s = c["t"].sup
+    assert (s.state, s.last_state) == (T.TERMINATE, T.GRIDLOCK) and c["t"].done
+    assert not c["ca"][:, :n - 2].any() and c["ca"][:, n - 2].any() and c["ca"][:, n - 1].any()
+    assert (c["t"].state.P == np.arange(n)).all()
+    # reassign: a counted assignment message within the steps of the batch
+    assert 0 < d["rise"] < steps, d["rise"]
+    # two_formations: a whole record
+    (e,), _ = _fly(C.batch([C.two_formations(n)]), steps_e)
+    r = e["t"].sup.record()
+    assert r["state"] == T.COMPLETE and r["assignments"] == [1, 1] and min(r["time"]) > 0
+
+
+def test_trial_cases_reach_their_ends_on_cpu():
+    """What tests/test_gpu_trial.py flies at n = 65 covers its edges on the
+    restatement alone (the steps are that test's)."""
+    _check_cases_on_cpu(65, 240, 390)
+
+
+@pytest.mark.slow
+def test_trial_cases_reach_their_ends_on_cpu_n129():
+    _check_cases_on_cpu(129, 246, 620)
+
+
+# -- engine.Trial: the arguments ------------------------------------------
+
+def _tables():
+    import torch  # noqa: F401
+    from aclswarm_amd import engine
+    pts, adj, gains, _ = H.swarm6()
+    return (engine.FormationTable.from_host(pts, adj, gains, device="cpu"),
+            engine.FormationTable.from_host(pts, adj, gains, device="meta"))
+
+
+def test_engine_trial_validates_before_anything_runs(monkeypatch):
+    """Each malformed argument raises ValueError before the library is loaded
+    or anything is allocated (host and meta tensors: no device is touched)."""
+    import torch
+    from aclswarm_amd import _lib as L
+    from aclswarm_amd import engine
+    Tc, Tm = _tables()
+
+    def no_lib():
+        raise AssertionError("Trial loaded the library")
+    monkeypatch.setattr(L, "lib", no_lib)
+    n, B, K = Tc.n, 4, 2
+    meta = torch.device("meta")
+
+    def good(dev="cpu"):
+        return dict(fseq=torch.zeros((B, K), dtype=torch.int32, device=dev),
+                    q=torch.zeros((B, n, 3), dtype=torch.float64, device=dev),
+                    vel=torch.zeros((B, n, 3), dtype=torch.float64, device=dev))
+    g = good()
+    bad = [
+        ("fseq", g["fseq"].to(torch.int64)),                          # dtype
+        ("q", g["q"].to(torch.float32)),
+        ("vel", g["vel"].to(torch.float32)),
+        ("fseq", torch.zeros(B, dtype=torch.int32)),                  # shape
+        ("fseq", torch.zeros((B + 1, K), dtype=torch.int32)),
+        ("fseq", torch.zeros((B, 0), dtype=torch.int32)),             # K >= 1
+        ("q", torch.zeros((B, n + 1, 3), dtype=torch.float64)),       # n is the table's
+        ("q", torch.zeros((B, n), dtype=torch.float64)),
+        ("vel", torch.zeros((B + 1, n, 3), dtype=torch.float64)),
+        ("vel", torch.zeros((B, n, 2), dtype=torch.float64)),
+        ("fseq", torch.zeros((K, B), dtype=torch.int32).t()),         # not contiguous
+        ("q", torch.zeros((B, 3, n), dtype=torch.float64).transpose(1, 2)),
+        ("vel", torch.zeros((2 * B, n, 3), dtype=torch.float64)[::2]),
+        ("fseq", torch.zeros((B, K), dtype=torch.int32, device=meta)),   # mixed devices
+        ("vel", torch.zeros((B, n, 3), dtype=torch.float64, device=meta)),
+        ("fseq", np.zeros((B, K), np.int32)),                         # not tensors
+        ("q", np.zeros((B, n, 3))),
+        ("vel", None),
+    ]
+    for name, t in bad:
+        kw = dict(g)
+        kw[name] = t
+        with pytest.raises(ValueError, match="Trial: " + name):
+            engine.Trial(Tc, **kw)
+    with pytest.raises(ValueError, match="formation table"):
+        engine.Trial(Tm, **g)
+    with pytest.raises(ValueError, match="formation table"):
+        engine.Trial(Tc, **good(meta))
+    # consistent tensors that are not on a CUDA device
+    with pytest.raises(ValueError, match="CUDA"):
+        engine.Trial(Tc, **g)
+    with pytest.raises(ValueError, match="CUDA"):
+        engine.Trial(Tm, **good(meta))
 
 
 # -- ABI ------------------------------------------------------------------

@@ -38,6 +38,7 @@ EXPORTS = (
     "acl_control_batch", "acl_write_assignment_log", "acl_read_assignment_log",
     "acl_hungarian_batch", "acl_cbaa_step_batch", "acl_vehicle_start_batch",
     "acl_fleet_workspace_bytes", "acl_fleet_auction_batch",
+    "acl_fleet_episode_workspace_bytes", "acl_fleet_episode_batch",
     "acl_default_episode_params", "acl_episode_workspace_bytes", "acl_episode_batch",
     "acl_default_trial_params", "acl_trial_workspace_bytes", "acl_trial_init", "acl_trial_batch",
     "acl_generate_formation_groups",
@@ -174,6 +175,25 @@ class EpisodeArgs(ct.Structure):
                 ("ep", EpisodeParams)]
 
 
+class FleetEpisodeArgs(ct.Structure):
+    """acl_fleet_episode_args_t (added within ABI 11): closed-loop episodes on
+    the message-level auction."""
+    _fields_ = [(n, ct.c_int32) for n in ("B", "step0", "steps", "ticks_per_step", "max_iter",
+                                          "queue_cap")] + [
+        (n, ct.c_void_p) for n in (
+            "fidx", "q", "vel", "P", "Pt", "open", "invalid", "just_received", "biditer", "price",
+            "who", "Rt", "final_price", "final_who", "done_tick", "vflags", "n_thrown", "n_tally",
+            "queue_len", "status", "adopt_step", "est", "ring_u", "ring_ca", "q_hist", "vel_hist",
+            "u_hist", "ca_hist", "P_hist", "vflags_hist", "fst", "workspace")] + [
+        ("workspace_bytes", ct.c_size_t), ("cntrl", CntrlGains), ("safety", SafetyParams),
+        ("ep", EpisodeParams)]
+
+
+FLEET_EPISODE_STATUS_DTYPE = np.dtype([(k, "<i4") for k in (
+    "flags", "ticks_run", "n_started", "n_restarted", "n_flushed", "n_consensus", "n_adopted",
+    "n_invalid")])
+
+
 class TrialParams(ct.Structure):
     """acl_trial_params_t (supervisor.py:47-62,88,121; coordination.launch:5)."""
     _fields_ = [("ep", EpisodeParams), ("tick_rate", ct.c_int32), ("settle_steps", ct.c_int32),
@@ -292,6 +312,11 @@ def lib():
     L.acl_fleet_auction_batch.argtypes = [ct.POINTER(Formations), ct.POINTER(FleetAuctionArgs),
                                           VP]
     L.acl_fleet_auction_batch.restype = ct.c_int
+    L.acl_fleet_episode_workspace_bytes.argtypes = [I32, I32, I32]
+    L.acl_fleet_episode_workspace_bytes.restype = SZ
+    L.acl_fleet_episode_batch.argtypes = [ct.POINTER(Formations), ct.POINTER(FleetEpisodeArgs),
+                                          VP]
+    L.acl_fleet_episode_batch.restype = ct.c_int
     L.acl_write_assignment_log.argtypes = [ct.c_char_p, I32, VP, VP, VP, VP, VP, VP]
     L.acl_write_assignment_log.restype = ct.c_int
     L.acl_read_assignment_log.argtypes = [ct.c_char_p, ct.POINTER(I32), VP, VP, VP, VP, VP, VP]

@@ -12,7 +12,7 @@
 //   central_kernel ACL_ASSIGN_CENTRAL: the operator's Hungarian assignment as
 //                  every vehicle's setAssignment + newAssignmentCb
 //                  (coordination_ros.cpp:330-343)
-//   traj_kernel    Safety::makeSafeTraj (safety.cpp:330-408) with the
+//   traj_kernel    (episode_dev.h) Safety::makeSafeTraj (safety.cpp:330-408) with the
 //                  utils::rateLimit / clamp helpers (utils.h:213-264), the
 //                  perfectly tracking vehicle (q <- goal.pos, vel <-
 //                  goal.vel), and the supervisor's windowed predicates
@@ -235,105 +235,6 @@ __global__ void __launch_bounds__(256) central_kernel(const CentralArgs A) {
   }
 }
 
-struct TrajParams {
-  int n, B, step, k, tick;
-  double* q;
-  double* vel;
-  const double* u;
-  const double* us;
-  const uint8_t* ca;
-  const uint16_t* P;
-  acl_episode_status_t* est;
-  double* ring_u;
-  uint8_t* ring_ca;
-  double* q_hist;
-  double* vel_hist;
-  double* u_hist;
-  uint8_t* ca_hist;
-  uint16_t* P_hist;
-  unsigned* ca_count;  // the control stage's collision-avoidance count
-  acl_episode_params_t ep;
-};
-
-__global__ void __launch_bounds__(kEpBlock) traj_kernel(const TrajParams T) {
-  __shared__ int s_all_conv, s_any_grid, s_nca;
-  const int n = T.n, b = blockIdx.x, tid = threadIdx.x;
-  const acl_episode_params_t ep = T.ep;
-  if (tid == 0) {
-    s_all_conv = 1;
-    s_any_grid = 0;
-    s_nca = 0;
-    // ca_kernel has consumed the list (stream order): reset for the next step
-    if (b == 0) *T.ca_count = 0u;
-  }
-  __syncthreads();
-  const uint32_t m0 = T.est[b].n_samples;  // ticks before this one
-  const int L = ep.bufflen;
-  int nca = 0;
-  for (int v = tid; v < n; v += (int)blockDim.x) {
-    const size_t iv = (size_t)b * n + v;
-    double gp[3] = {T.q[3 * iv], T.q[3 * iv + 1], T.q[3 * iv + 2]};
-    double gv[3] = {T.vel[3 * iv], T.vel[3 * iv + 1], T.vel[3 * iv + 2]};
-    double c[3] = {T.us[3 * iv], T.us[3 * iv + 1], T.us[3 * iv + 2]};
-    make_safe_traj(ep, gp, gv, c);
-    // the vehicle tracks its goal exactly
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      T.q[3 * iv + a] = gp[a];
-      T.vel[3 * iv + a] = gv[a];
-    }
-    const uint8_t cav = T.ca[iv];
-    nca += cav != 0;
-    const size_t ih = (size_t)T.k * T.B * n + iv;
-    if (T.q_hist)
-      for (int a = 0; a < 3; ++a) T.q_hist[3 * ih + a] = gp[a];
-    if (T.vel_hist)
-      for (int a = 0; a < 3; ++a) T.vel_hist[3 * ih + a] = gv[a];
-    if (T.u_hist)
-      for (int a = 0; a < 3; ++a) T.u_hist[3 * ih + a] = T.u[3 * iv + a];
-    if (T.ca_hist) T.ca_hist[ih] = cav;
-    if (T.P_hist) T.P_hist[ih] = T.P[iv];
-    if (T.tick) {
-      // supervisor tick: |voriggoal| (the DistCntrl command) and the CA flag
-      // enter the ring; with a full window, the per-vehicle means
-      const double u0 = T.u[3 * iv], u1 = T.u[3 * iv + 1], u2 = T.u[3 * iv + 2];
-      const double speed = sqrt((u0 * u0 + u1 * u1) + u2 * u2);
-      double* ru = T.ring_u + (size_t)b * L * n;
-      uint8_t* rc = T.ring_ca + (size_t)b * L * n;
-      ru[(size_t)(m0 % L) * n + v] = speed;
-      rc[(size_t)(m0 % L) * n + v] = cav;
-      const uint32_t m = m0 + 1;
-      if (m >= (uint32_t)L) {
-        double su = 0.0, sc = 0.0;
-        for (int i = 0; i < L; ++i) {  // oldest -> newest (deque order)
-          const size_t slot = (size_t)((m - L + i) % L) * n + v;
-          su = su + ru[slot];
-          sc = sc + (double)rc[slot];
-        }
-        const double mu = su / (double)L, mc = sc / (double)L;
-        if (!(mu < ep.orig_zero_vel_thr)) atomicAnd(&s_all_conv, 0);
-        if (mc > ep.avg_active_ca_thr) atomicOr(&s_any_grid, 1);
-      }
-    }
-  }
-  if (nca) atomicAdd(&s_nca, nca);
-  __syncthreads();
-  if (tid == 0) {
-    acl_episode_status_t e = T.est[b];
-    e.n_ca_steps += (uint32_t)s_nca;
-    if (T.tick) {
-      e.n_samples = m0 + 1;
-      if (m0 + 1 >= (uint32_t)L) {
-        e.converged = s_all_conv;
-        e.gridlocked = s_any_grid;
-        if (s_all_conv && e.converged_step < 0) e.converged_step = T.step;
-        if (s_any_grid && e.gridlock_step < 0) e.gridlock_step = T.step;
-      }
-    }
-    T.est[b] = e;
-  }
-}
-
 }  // namespace acl_amd
 
 extern "C" void acl_default_episode_params(acl_episode_params_t* e) {
@@ -483,7 +384,7 @@ extern "C" acl_status_t acl_episode_batch(const acl_formations_t* F, const acl_e
     T.step = step;
     T.k = k;
     T.tick = (step % ep.sample_every) == 0;
-    hipLaunchKernelGGL(traj_kernel, dim3(B), dim3(n <= 64 ? 64 : kEpBlock), 0, s, T);
+    hipLaunchKernelGGL(traj_kernel<false>, dim3(B), dim3(n <= 64 ? 64 : kEpBlock), 0, s, T);
     if (hipGetLastError() != hipSuccess) return acl__set_error("traj_kernel launch failed");
   }
   return ACL_OK;

@@ -1,0 +1,384 @@
+// fleet_episode.hip -- closed-loop episodes on the message-level auction.
+//
+// acl_fleet_episode_batch flies B swarms of n <= 128 vehicles with every
+// vehicle its own Auctioneer (acl_fleet_auction_batch, fleet_auction.hip)
+// in place of the synchronous auction and the swarm-level flush rule of
+// acl_episode_batch; include/aclswarm_amd.h states the model. Per control
+// step the host loop enqueues
+//   fleet_cmd_kernel      (auto-auction steps) every vehicle's own
+//                         CoordinationROS::autoauctionCb
+//                         (coordination_ros.cpp:322-359): FLUSH when its last
+//                         auction converged on an invalid table, else START
+//                         (a restart when its auctioneer is open)
+//   fleet_auction_kernel  ticks_per_step auctioneer ticks (called through
+//                         acl_fleet_auction_batch, not edited)
+//   fleet_handoff_kernel  the flags the ticks raised -> counters, adopt_step,
+//                         vflags_hist; when a vehicle adopted, the control
+//                         hand-off from the vehicles' rows (newAssignmentCb,
+//                         :284-303): one table (mode 0) when all n rows are
+//                         equal, else per-vehicle rows (mode 1)
+//   run_control           DistCntrl + saturation + collision avoidance
+//                         (control.hip, CTL_MIXED)
+//   traj_kernel<true>     makeSafeTraj, the tracking vehicle and the
+//                         supervisor ring (episode_dev.h)
+// One workgroup per swarm in the two new kernels; both are O(n) .. O(n^2)
+// integer work per swarm and latency-bound: the step's time is the fleet
+// kernel's ticks and the control stage's gain stream.
+//
+// A swarm whose fidx is out of range or that holds a row that is no
+// permutation at the start of the call is flagged once, by the call's first
+// fleet_handoff_kernel launch (before any tick): the fleet kernel sees fidx
+// -1 for it, the control kernels a BAD_INPUT status, traj_kernel its skip
+// flag -- nothing of the swarm's state is written.
+#include "common.h"
+#include "episode_dev.h"
+
+#include "../../include/aclswarm_amd.h"
+
+extern "C" acl_status_t acl__set_error(const char* msg);
+
+namespace acl_amd {
+
+constexpr int kFepMaxN = 128;
+constexpr int kFepBlock = 256;  // fleet_handoff_kernel: 4 waves, rows v = wave, wave + 4, ...
+
+// Workspace: the fleet kernel's own, then the control stage's hand-off
+// region (a WsLayout: pt, mode, rows, ...), its status and outputs, and the
+// loop's own small arrays.
+struct FepLayout {
+  size_t fleet, ctl, cst, u, us, ca, cmd, vf, fidx, skip, total;
+};
+
+inline FepLayout fep_layout(int n, int B, int cap) {
+  FepLayout L;
+  const size_t nb = (size_t)n, bb = (size_t)B;
+  size_t o = 0;
+  L.fleet = o; o = ws_al(o + acl_fleet_workspace_bytes(n, B, cap));
+  L.ctl = o;   o = ws_al(o + ws_layout(n, B).total);
+  L.cst = o;   o = ws_al(o + bb * sizeof(acl_swarm_status_t));
+  L.u = o;     o = ws_al(o + bb * nb * 3 * 8);
+  L.us = o;    o = ws_al(o + bb * nb * 3 * 8);
+  L.ca = o;    o = ws_al(o + bb * nb);
+  L.cmd = o;   o = ws_al(o + bb * nb);      // [B][n] u8: this auto-auction's commands
+  L.vf = o;    o = ws_al(o + bb * nb * 4);  // [B][n] i32: the ACL_FLEET_V_* of this step's ticks
+  L.fidx = o;  o = ws_al(o + bb * 4);       // [B] i32: fidx, -1 for a BAD_INPUT swarm
+  L.skip = o;  o = ws_al(o + bb);           // [B] u8: BAD_INPUT in this call
+  L.total = o;
+  return L;
+}
+
+struct FepArgs {
+  int n, B, F, step, k;
+  const int32_t* fidx;
+  int32_t* fidx_eff;
+  uint8_t* skip;
+  const uint16_t* Pt;
+  const uint8_t* open;
+  const uint8_t* invalid;
+  uint8_t* cmd;
+  int32_t* vf;
+  int32_t* vflags;
+  int32_t* vflags_hist;
+  int32_t* adopt_step;
+  const acl_fleet_status_t* status;
+  acl_fleet_episode_status_t* fst;
+  acl_episode_status_t* est;
+  uint16_t* P;
+  uint16_t* ctlPt;
+  uint8_t* ctlMode;
+  uint16_t* ctlRows;
+  acl_swarm_status_t* cst;
+};
+
+// CoordinationROS::autoauctionCb of every vehicle (coordination_ros.cpp:
+// 339-358) as the fleet kernel's commands, and the counts of what was asked.
+__global__ void __launch_bounds__(kFepMaxN) fleet_cmd_kernel(const FepArgs A) {
+  __shared__ int cnt_s[3];
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x, n = A.n;
+  if (A.skip[b] != 0) return;  // block-uniform: the fleet kernel skips the swarm too
+  if (tid < 3) cnt_s[tid] = 0;
+  __syncthreads();
+  const size_t vb = (size_t)b * n;
+  int c = ACL_FLEET_NONE;
+  bool busy = false;
+  if (tid < n) {
+    c = A.invalid[vb + tid] != 0 ? ACL_FLEET_FLUSH : ACL_FLEET_START;
+    busy = A.open[vb + tid] != 0;
+    A.cmd[vb + tid] = (uint8_t)c;
+  }
+  const int ns = __popcll(__ballot(c == ACL_FLEET_START));
+  const int nr = __popcll(__ballot(c == ACL_FLEET_START && busy));
+  const int nf = __popcll(__ballot(c == ACL_FLEET_FLUSH));
+  if ((tid & 63) == 0) {
+    if (ns) atomicAdd(&cnt_s[0], ns);
+    if (nr) atomicAdd(&cnt_s[1], nr);
+    if (nf) atomicAdd(&cnt_s[2], nf);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    acl_fleet_episode_status_t s = A.fst[b];
+    s.n_started += cnt_s[0];
+    s.n_restarted += cnt_s[1];
+    s.n_flushed += cnt_s[2];
+    A.fst[b] = s;
+  }
+}
+
+// kFirst (the call's first launch, before any tick): the swarm's input check
+// and its hand-off from the rows alone. Otherwise (after each step's ticks):
+// the flags of the step, and the hand-off again when a vehicle adopted.
+template <bool kFirst>
+__global__ void __launch_bounds__(kFepBlock) fleet_handoff_kernel(const FepArgs A) {
+  __shared__ int cnt_s[3];
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x, n = A.n;
+  const int lane = tid & 63, wv = tid >> 6;
+  const size_t vb = (size_t)b * n;
+  const uint16_t* rows = A.Pt + vb * n;
+  bool differs = false;  // some row is not row 0
+  if (kFirst) {
+    const int f = A.fidx[b];
+    bool bad = f < 0 || f >= A.F;
+    const unsigned long long lastmask = (n & 63) ? ((1ull << (n & 63)) - 1ull) : ~0ull;
+    const unsigned long long full0 = n > 64 ? ~0ull : lastmask;
+    const unsigned long long full1 = n > 64 ? lastmask : 0ull;
+    for (int v = wv; v < n; v += kFepBlock / 64) {
+      // a permutation <=> n entries below n that set n different bits
+      unsigned w0 = 0u, w1 = 0u, w2 = 0u, w3 = 0u;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int j = lane + 64 * s;
+        if (j < n) {
+          const unsigned x = rows[(size_t)v * n + j];
+          if (x >= (unsigned)n) bad = true;
+          else {
+            const unsigned bit = 1u << (x & 31);
+            const unsigned wd = x >> 5;
+            if (wd == 0) w0 |= bit;
+            else if (wd == 1) w1 |= bit;
+            else if (wd == 2) w2 |= bit;
+            else w3 |= bit;
+            if (x != rows[j]) differs = true;
+          }
+        }
+      }
+      w0 = wave_or_u32(w0);
+      w1 = wave_or_u32(w1);
+      w2 = wave_or_u32(w2);
+      w3 = wave_or_u32(w3);
+      if ((((unsigned long long)w1 << 32) | w0) != full0 ||
+          (((unsigned long long)w3 << 32) | w2) != full1)
+        bad = true;
+    }
+    bad = __syncthreads_or(bad) != 0;
+    if (tid == 0) {
+      A.fidx_eff[b] = bad ? -1 : f;
+      A.skip[b] = bad ? 1 : 0;
+      A.fst[b].flags = (A.fst[b].flags & ACL_FLEET_OVERFLOW) | (bad ? ACL_FLEET_BAD_INPUT : 0);
+      if (bad) {
+        acl_swarm_status_t st = {};
+        st.flags = ACL_SWARM_BAD_INPUT;  // the control kernels leave the swarm alone
+        A.cst[b] = st;
+      }
+    }
+    if (bad) return;
+  } else {
+    if (A.skip[b] != 0) {  // block-uniform
+      if (A.vflags_hist && tid < n) A.vflags_hist[((size_t)A.k * A.B + b) * n + tid] = 0;
+      return;
+    }
+    if (tid < 3) cnt_s[tid] = 0;
+    __syncthreads();
+    int x = 0;
+    if (tid < n) {
+      x = A.vf[vb + tid];
+      if (x) {
+        A.vflags[vb + tid] |= x;
+        A.vf[vb + tid] = 0;
+        if (x & ACL_FLEET_V_ADOPTED) A.adopt_step[vb + tid] = A.step;
+      }
+      if (A.vflags_hist) A.vflags_hist[((size_t)A.k * A.B + b) * n + tid] = x;
+    }
+    const int nc = __popcll(__ballot((x & ACL_FLEET_V_CONSENSUS) != 0));
+    const int na = __popcll(__ballot((x & ACL_FLEET_V_ADOPTED) != 0));
+    const int ni = __popcll(__ballot((x & ACL_FLEET_V_INVALID) != 0));
+    if (lane == 0) {
+      if (nc) atomicAdd(&cnt_s[0], nc);
+      if (na) atomicAdd(&cnt_s[1], na);
+      if (ni) atomicAdd(&cnt_s[2], ni);
+    }
+    __syncthreads();
+    const int adopted = cnt_s[1];
+    if (tid == 0) {
+      const acl_fleet_status_t fs = A.status[b];
+      acl_fleet_episode_status_t s = A.fst[b];
+      s.ticks_run += fs.ticks_run;
+      s.flags |= fs.flags & ACL_FLEET_OVERFLOW;
+      s.n_consensus += cnt_s[0];
+      s.n_adopted += adopted;
+      s.n_invalid += cnt_s[2];
+      A.fst[b] = s;
+    }
+    if (adopted == 0) return;  // the tables the vehicles fly are unchanged
+    // are the n rows one table? every entry against row 0's, a wave per row
+    for (int v = wv; v < n; v += kFepBlock / 64) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int j = lane + 64 * s;
+        if (j < n && rows[(size_t)v * n + j] != rows[j]) differs = true;
+      }
+    }
+  }
+  const bool mixed = __syncthreads_or(__any(differs)) != 0;
+  // the control hand-off, in adopt_kernel's layouts (episode.hip). The rows
+  // are permutations: checked at the start of the call, and the fleet kernel
+  // adopts valid tables only.
+  if (!mixed) {
+    for (int j = tid; j < n; j += kFepBlock) {
+      const uint16_t v = rows[j];
+      A.ctlPt[vb + j] = v;
+      A.P[vb + v] = (uint16_t)j;
+    }
+  } else {
+    uint16_t* crows = A.ctlRows + vb * n;
+    for (int v = wv; v < n; v += kFepBlock / 64) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int j = lane + 64 * s;
+        if (j < n) {
+          const uint16_t x = rows[(size_t)v * n + j];
+          crows[(size_t)v * n + j] = x;
+          if ((int)x == v) A.P[vb + v] = (uint16_t)j;  // the vehicle's point in its own row
+        }
+      }
+    }
+  }
+  if (tid == 0) {
+    A.ctlMode[b] = mixed ? 1 : 0;
+    A.est[b].per_vehicle = mixed ? 1 : 0;
+    A.cst[b] = acl_swarm_status_t{};
+  }
+}
+
+}  // namespace acl_amd
+
+extern "C" size_t acl_fleet_episode_workspace_bytes(int32_t n, int32_t B, int32_t queue_cap) {
+  if (n < 1 || n > acl_amd::kFepMaxN || B < 1 || queue_cap < 1) return 0;
+  return acl_amd::fep_layout(n, B, queue_cap).total;
+}
+
+extern "C" acl_status_t acl_fleet_episode_batch(const acl_formations_t* F,
+                                                const acl_fleet_episode_args_t* a, void* stream) {
+  using namespace acl_amd;
+  if (!F || !a) return acl__set_error("acl_fleet_episode_batch: null argument");
+  const int n = F->n, B = a->B;
+  if (n < 1 || n > kFepMaxN)
+    return acl__set_error("acl_fleet_episode_batch: n out of range [1, 128]");
+  if (B < 0 || a->steps < 0 || a->step0 < 0)
+    return acl__set_error("acl_fleet_episode_batch: B, steps and step0 must be >= 0");
+  if (a->ticks_per_step < 1)
+    return acl__set_error("acl_fleet_episode_batch: ticks_per_step < 1");
+  if (a->max_iter < 0) return acl__set_error("acl_fleet_episode_batch: max_iter < 0");
+  if (a->queue_cap < 1) return acl__set_error("acl_fleet_episode_batch: queue_cap < 1");
+  const acl_episode_params_t& ep = a->ep;
+  if (ep.auction_latency != 0 || ep.assignment != ACL_ASSIGN_CBAA)
+    return acl__set_error("acl_fleet_episode_batch: ep.auction_latency and ep.assignment must "
+                          "be 0 (the auction takes the time its messages take)");
+  if (ep.auction_every < 1 || ep.sample_every < 1 || ep.bufflen < 1 || !(ep.control_dt > 0.0))
+    return acl__set_error("acl_fleet_episode_batch: auction_every, sample_every, bufflen must "
+                          "be >= 1 and control_dt > 0");
+  if (B == 0 || a->steps == 0) return ACL_OK;
+  if (!a->fidx || !a->q || !a->vel || !a->P || !a->Pt || !a->open || !a->invalid ||
+      !a->just_received || !a->biditer || !a->price || !a->who || !a->Rt || !a->final_price ||
+      !a->final_who || !a->done_tick || !a->vflags || !a->n_thrown || !a->n_tally ||
+      !a->queue_len || !a->status || !a->adopt_step || !a->est || !a->ring_u || !a->ring_ca ||
+      !a->fst || !a->workspace)
+    return acl__set_error("acl_fleet_episode_batch: required pointer is NULL");
+  if (a->workspace_bytes < acl_fleet_episode_workspace_bytes(n, B, a->queue_cap))
+    return acl__set_error("acl_fleet_episode_batch: workspace_bytes is too small "
+                          "(acl_fleet_episode_workspace_bytes)");
+  const FepLayout W = fep_layout(n, B, a->queue_cap);
+  const WsLayout WS = ws_layout(n, B);
+  unsigned char* ws = (unsigned char*)a->workspace;
+  unsigned char* wc = ws + W.ctl;  // the control stage's hand-off region
+  hipStream_t s = (hipStream_t)stream;
+  double* u = reinterpret_cast<double*>(ws + W.u);
+  double* us = reinterpret_cast<double*>(ws + W.us);
+  uint8_t* ca = ws + W.ca;
+  uint8_t* cmd = ws + W.cmd;
+  int32_t* fidx_eff = reinterpret_cast<int32_t*>(ws + W.fidx);
+
+  FepArgs A;
+  A.n = n; A.B = B; A.F = F->n_formations; A.step = a->step0; A.k = 0;
+  A.fidx = a->fidx; A.fidx_eff = fidx_eff; A.skip = ws + W.skip;
+  A.Pt = a->Pt; A.open = a->open; A.invalid = a->invalid; A.cmd = cmd;
+  A.vf = reinterpret_cast<int32_t*>(ws + W.vf);
+  A.vflags = a->vflags; A.vflags_hist = a->vflags_hist; A.adopt_step = a->adopt_step;
+  A.status = a->status; A.fst = a->fst; A.est = a->est; A.P = a->P;
+  A.ctlPt = reinterpret_cast<uint16_t*>(wc + WS.pt);
+  A.ctlMode = wc + WS.mode;
+  A.ctlRows = reinterpret_cast<uint16_t*>(wc + WS.rows);
+  A.cst = reinterpret_cast<acl_swarm_status_t*>(ws + W.cst);
+
+  // the ticks: the fleet kernel on the episode's state; its vflags are the
+  // step's own (A.vf, cleared by the hand-off), the caller's stay sticky
+  acl_fleet_auction_args_t fa = {};
+  fa.B = B; fa.ticks = a->ticks_per_step; fa.max_iter = a->max_iter; fa.queue_cap = a->queue_cap;
+  fa.fidx = fidx_eff; fa.q = a->q; fa.Pt = a->Pt; fa.open = a->open; fa.invalid = a->invalid;
+  fa.just_received = a->just_received; fa.biditer = a->biditer; fa.price = a->price;
+  fa.who = a->who; fa.Rt = a->Rt; fa.final_price = a->final_price; fa.final_who = a->final_who;
+  fa.done_tick = a->done_tick; fa.vflags = A.vf; fa.n_thrown = a->n_thrown;
+  fa.n_tally = a->n_tally; fa.queue_len = a->queue_len; fa.status = a->status;
+  fa.workspace = ws + W.fleet;
+  fa.workspace_bytes = acl_fleet_workspace_bytes(n, B, a->queue_cap);
+
+  acl_control_args_t cs = {};
+  cs.B = B; cs.fidx = fidx_eff; cs.q = a->q; cs.vel = a->vel; cs.P = a->P;
+  cs.u = u; cs.u_safe = us; cs.ca_flag = ca; cs.status = A.cst;
+  cs.workspace = wc; cs.cntrl = a->cntrl; cs.safety = a->safety;
+
+  TrajParams T;
+  T.n = n; T.B = B; T.q = a->q; T.vel = a->vel; T.u = u; T.us = us; T.ca = ca; T.P = a->P;
+  T.est = a->est; T.ring_u = a->ring_u; T.ring_ca = a->ring_ca;
+  T.q_hist = a->q_hist; T.vel_hist = a->vel_hist; T.u_hist = a->u_hist; T.ca_hist = a->ca_hist;
+  T.P_hist = a->P_hist;
+  T.ep = ep;
+  T.skip = A.skip;
+  {
+    // the collision-avoidance count is zeroed by traj_kernel after each step
+    CtlParams C;
+    const acl_status_t r = ctl_params(F, &cs, C);
+    if (r != ACL_OK) return r;
+    T.ca_count = C.ca_count;
+    if (hipMemsetAsync(C.ca_count, 0, kCaCounterBytes, s) != hipSuccess)
+      return acl__set_error("hipMemsetAsync failed");
+  }
+  // the call's input check and its hand-off from the rows alone
+  hipLaunchKernelGGL(fleet_handoff_kernel<true>, dim3(B), dim3(kFepBlock), 0, s, A);
+  if (hipGetLastError() != hipSuccess)
+    return acl__set_error("fleet_handoff_kernel launch failed");
+  for (int k = 0; k < a->steps; ++k) {
+    const int step = a->step0 + k;
+    A.step = step;
+    A.k = k;
+    const bool auction = step % ep.auction_every == 0;
+    if (auction) {
+      hipLaunchKernelGGL(fleet_cmd_kernel, dim3(B), dim3(kFepMaxN), 0, s, A);
+      if (hipGetLastError() != hipSuccess)
+        return acl__set_error("fleet_cmd_kernel launch failed");
+    }
+    fa.cmd = auction ? cmd : nullptr;
+    acl_status_t r = acl_fleet_auction_batch(F, &fa, stream);
+    if (r != ACL_OK) return r;
+    hipLaunchKernelGGL(fleet_handoff_kernel<false>, dim3(B), dim3(kFepBlock), 0, s, A);
+    if (hipGetLastError() != hipSuccess)
+      return acl__set_error("fleet_handoff_kernel launch failed");
+    r = run_control(F, &cs, s, CTL_MIXED);
+    if (r != ACL_OK) return r;
+    T.step = step;
+    T.k = k;
+    T.tick = (step % ep.sample_every) == 0;
+    hipLaunchKernelGGL(traj_kernel<true>, dim3(B), dim3(n <= 64 ? 64 : kEpBlock), 0, s, T);
+    if (hipGetLastError() != hipSuccess) return acl__set_error("traj_kernel launch failed");
+  }
+  return ACL_OK;
+}

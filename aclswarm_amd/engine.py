@@ -718,6 +718,161 @@ class Episode:
         return arr.view(L.EPISODE_STATUS_DTYPE).reshape(-1)
 
 
+class FleetEpisode:
+    """Closed-loop episodes on the message-level auction
+    (acl_fleet_episode_batch, added within ABI 11): B swarms of n <= 128
+    vehicles, every vehicle its own Auctioneer (FleetAuction's model) with its
+    own auto-auction rule, ticks_per_step auctioneer ticks per control step,
+    and each vehicle's controller switching to its own table at the step it
+    adopts. include/aclswarm_amd.h states the model and its limits.
+
+    fidx [B] int32, q/vel [B][n][3] f64, Pt [B][n][n] int16 (uint16 bits;
+    vehicle v's own row, formation point -> vehicle; None: identity rows), all
+    on the table's device; they are copied. queue_cap None: 4 n; max_iter 0:
+    2 n. The object owns the state the way Episode and FleetAuction do: q,
+    vel, P (each vehicle's point in its own row), the fleet state (Pt, open,
+    invalid, just_received, biditer, price, who, Rt) and outputs (final_price,
+    final_who, done_tick, vflags, n_thrown, n_tally, queue_len), adopt_step,
+    the supervisor's rings and both status arrays. just_received starts at 1
+    and adopt_step at -1; the caller may rewrite any state tensor between
+    runs. Raises ValueError on a malformed argument before anything runs."""
+
+    FLEET_KEYS = ("Pt", "open", "invalid", "just_received", "biditer", "price", "who", "Rt",
+                  "final_price", "final_who", "done_tick", "vflags", "n_thrown", "n_tally",
+                  "queue_len")
+
+    def __init__(self, table, fidx, q, vel, Pt=None, params=None, cntrl=None, safety=None,
+                 queue_cap=None, max_iter=0, ticks_per_step=10):
+        n = table.n
+        if n < 1 or n > L.FLEET_MAX_N:
+            raise ValueError(f"FleetEpisode: n = {n} out of range [1, {L.FLEET_MAX_N}]")
+        if not isinstance(q, torch.Tensor) or q.dim() != 3:
+            raise ValueError(f"FleetEpisode: q must be a torch.float64 tensor of shape [B][{n}][3]")
+        B = int(q.shape[0])
+        if B < 1:
+            raise ValueError("FleetEpisode: q is empty")
+        if queue_cap is None:
+            queue_cap = 4 * n
+        if int(queue_cap) < 1:
+            raise ValueError(f"FleetEpisode: queue_cap = {queue_cap} < 1")
+        if int(max_iter) < 0:
+            raise ValueError(f"FleetEpisode: max_iter = {max_iter} < 0")
+        if int(ticks_per_step) < 1:
+            raise ValueError(f"FleetEpisode: ticks_per_step = {ticks_per_step} < 1")
+        if params is not None and (params.auction_latency != 0 or params.assignment != 0):
+            raise ValueError("FleetEpisode: params.auction_latency and params.assignment must "
+                             "be 0 (the auction takes the time its messages take)")
+        want = {"q": (q, torch.float64, (B, n, 3)), "vel": (vel, torch.float64, (B, n, 3)),
+                "fidx": (fidx, torch.int32, (B,))}
+        if Pt is not None:
+            want["Pt"] = (Pt, torch.int16, (B, n, n))
+        _check_state("FleetEpisode", table, want)
+        dev = q.device
+        if Pt is None:
+            Pt = torch.arange(n, dtype=torch.int16, device=dev).repeat(B, n, 1)
+        elif not torch.equal(torch.sort(Pt.to(torch.int32) & 0xFFFF, dim=2).values,
+                             torch.arange(n, dtype=torch.int32, device=dev).expand(B, n, n)):
+            raise ValueError(f"FleetEpisode: every row Pt[b][v] must be a permutation of "
+                             f"0..{n - 1}")
+        self.table, self.fidx, self.n, self.B, self.device = table, fidx, n, B, dev
+        self.queue_cap, self.max_iter = int(queue_cap), int(max_iter)
+        self.ticks_per_step = int(ticks_per_step)
+        self.ep = params or L.default_episode_params()
+        self.cntrl = cntrl or L.default_gains()
+        self.safety = safety or L.default_safety()
+        self.q = q.clone().contiguous()
+        self.vel = vel.clone().contiguous()
+        self.Pt = Pt.clone().contiguous()
+
+        def z(shape, dt, fill=0):
+            return torch.full(shape, fill, dtype=dt, device=dev)
+        # each vehicle's point in its own row (rewritten by every run)
+        own = (self.Pt.to(torch.int32) & 0xFFFF) == torch.arange(n, device=dev).view(1, n, 1)
+        self.P = own.to(torch.uint8).argmax(dim=2).to(torch.int16).contiguous()
+        self.open = z((B, n), torch.uint8)
+        self.invalid = z((B, n), torch.uint8)
+        self.just_received = z((B, n), torch.uint8, 1)
+        self.biditer = z((B, n), torch.int32)
+        self.price = z((B, n, n), torch.float32)
+        self.who = z((B, n, n), torch.int32, -1)
+        self.Rt = z((B, n, 6), torch.float64)
+        self.final_price = z((B, n, n), torch.float32)
+        self.final_who = z((B, n, n), torch.int32, -1)
+        self.done_tick = z((B, n), torch.int32, -1)
+        self.vflags = z((B, n), torch.int32)
+        self.n_thrown = z((B, n), torch.int32)
+        self.n_tally = z((B, n), torch.int32)
+        self.queue_len = z((B, n), torch.int32)
+        self.adopt_step = z((B, n), torch.int32, -1)
+        self._status = z((B, 4), torch.int32)
+        self.fst = z((B, L.FLEET_EPISODE_STATUS_DTYPE.itemsize), torch.uint8)
+        est = np.zeros(B, L.EPISODE_STATUS_DTYPE)
+        est["converged_step"] = -1
+        est["gridlock_step"] = -1
+        self.est = torch.from_numpy(est.view(np.uint8).reshape(B, -1).copy()).to(dev)
+        Lb = int(self.ep.bufflen)
+        self.ring_u = z((B, Lb, n), torch.float64)
+        self.ring_ca = z((B, Lb, n), torch.uint8)
+        self.ws = None  # allocated (zero-filled) by the first run
+        self.step = 0
+
+    def workspace_bytes(self):
+        return int(L.lib().acl_fleet_episode_workspace_bytes(self.n, self.B, self.queue_cap))
+
+    def run(self, steps, history=False, stream=None):
+        """Fly `steps` control periods. With history=True returns per-step
+        device tensors q/vel/u [steps][B][n][3], ca [steps][B][n], P
+        [steps][B][n] (int16) and vflags [steps][B][n] i32 (the FLEET_V_* of
+        _lib raised during the step; rows of BAD_INPUT swarms stay 0); else
+        None."""
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError(f"FleetEpisode.run: steps = {steps} < 0")
+        dev, B, n = self.device, self.B, self.n
+        if self.ws is None:
+            self.ws = torch.zeros(self.workspace_bytes(), dtype=torch.uint8, device=dev)
+        hist = None
+        if history:
+            hist = {
+                "q": torch.zeros((steps, B, n, 3), dtype=torch.float64, device=dev),
+                "vel": torch.zeros((steps, B, n, 3), dtype=torch.float64, device=dev),
+                "u": torch.zeros((steps, B, n, 3), dtype=torch.float64, device=dev),
+                "ca": torch.zeros((steps, B, n), dtype=torch.uint8, device=dev),
+                "P": torch.zeros((steps, B, n), dtype=torch.int16, device=dev),
+                "vflags": torch.zeros((steps, B, n), dtype=torch.int32, device=dev),
+            }
+        a = L.FleetEpisodeArgs()
+        a.B, a.step0, a.steps, a.ticks_per_step = B, self.step, steps, self.ticks_per_step
+        a.max_iter, a.queue_cap = self.max_iter, self.queue_cap
+        for k in ("fidx", "q", "vel", "P", "adopt_step", "est", "ring_u", "ring_ca", "fst") + \
+                self.FLEET_KEYS:
+            setattr(a, k, getattr(self, k).data_ptr())
+        a.status = self._status.data_ptr()
+        if hist is not None:
+            for k, v in hist.items():
+                setattr(a, k + "_hist", v.data_ptr())
+        a.workspace = self.ws.data_ptr()
+        a.workspace_bytes = self.ws.numel()
+        a.cntrl, a.safety, a.ep = self.cntrl, self.safety, self.ep
+        F = self.table.struct()
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        L.check(L.lib().acl_fleet_episode_batch(ct.byref(F), ct.byref(a), ct.c_void_p(stream)),
+                "acl_fleet_episode_batch")
+        self.step += steps
+        return hist
+
+    def status(self):
+        """{"episode": the acl_episode_status_t records, "fleet": the
+        acl_fleet_episode_status_t records, "ticks": the last step's
+        acl_fleet_status_t records}, structured numpy arrays [B]; synchronises."""
+        def view(t, dt):
+            return np.ascontiguousarray(t.cpu().numpy()).view(dt).reshape(-1)
+        return {"episode": view(self.est, L.EPISODE_STATUS_DTYPE),
+                "fleet": view(self.fst, L.FLEET_EPISODE_STATUS_DTYPE),
+                "ticks": view(self._status, L.FLEET_STATUS_DTYPE)}
+
+
 class Trial:
     """Batched Monte-Carlo trials (acl_trial_batch; supervisor.py over the
     closed loop): each swarm flies its formation sequence fseq[b] through the

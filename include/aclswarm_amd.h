@@ -824,6 +824,120 @@ size_t acl_episode_workspace_bytes(int32_t n, int32_t B);
 acl_status_t acl_episode_batch(const acl_formations_t* formations,
                                const acl_episode_args_t* args, void* stream);
 
+/* ---- episodes on the message-level auction (added within ABI 11) ----------
+ * acl_fleet_episode_batch flies B swarms of n <= 128 vehicles for `steps`
+ * control periods with every vehicle its own Auctioneer
+ * (acl_fleet_auction_batch) instead of the synchronous auction and the
+ * swarm-level flush rule of acl_episode_batch. An added symbol:
+ * ACL_ABI_VERSION stays 11 (no existing struct or call changed). Per global
+ * step s = step0 + k, every launch stream-ordered, nothing synchronises:
+ *   1. auto-auction: if s % auction_every == 0, every vehicle runs
+ *      CoordinationROS::autoauctionCb (coordination_ros.cpp:322-359) for
+ *      itself: a vehicle with invalid[b][v] != 0 (didConvergeOnInvalid-
+ *      Assignment) gets ACL_FLEET_FLUSH and does not start; every other
+ *      vehicle gets ACL_FLEET_START from the current q. A START on a vehicle
+ *      with open != 0 is a restart ("Auctioneer is busy! Restarting.",
+ *      :355-358). Per vehicle, not per swarm;
+ *   2. ticks: ticks_per_step auctioneer ticks (default 10: control_dt 10 ms
+ *      over auctioneer_dt 1 ms, coordination.launch:23,25; >= 1) of
+ *      acl_fleet_auction_batch on the episode's fleet state, with the
+ *      commands of (1) on auction steps and cmd = NULL otherwise; a quiescent
+ *      swarm stops inside the kernel;
+ *   3. hand-off (newAssignmentCb, :284-303): a vehicle that adopted during
+ *      this step's ticks flies its new row from this step's controller on.
+ *      When all n rows Pt[b][v][:] are equal the swarm flies one table
+ *      (control mode 0), otherwise each vehicle flies its own row (control
+ *      mode 1, est.per_vehicle = 1). P[b][v] is v's point in its own row;
+ *   4. control: DistCntrl + saturation + collision avoidance, as step 2 of
+ *      acl_episode_batch;
+ *   5. makeSafeTraj and the supervisor ring exactly as steps 3 and 4 of
+ *      acl_episode_batch: the same arithmetic, the same acl_episode_params_t
+ *      fields, the same acl_episode_status_t fields for converged / gridlock /
+ *      samples / CA steps. est's auction counters stay 0 except per_vehicle;
+ *      ep.auction_latency and ep.assignment must be 0.
+ * Model limits: the ticks of the interval [s T, (s + 1) T) run before step
+ * s's control; all vehicles' auto-auction timers fire on the same step; the
+ * limits of acl_fleet_auction_batch hold (latency below one tick, per-sender
+ * FIFO, queue_cap); the controller's first_assignment_ start is the trials'
+ * business and is not modelled; n <= 128.
+ * Device pointers, updated in place (an episode continues across calls):
+ *   fidx, q, vel, P, est, ring_u, ring_ca and the histories as in
+ *   acl_episode_args_t; the fleet state and output arrays as in
+ *   acl_fleet_auction_args_t (vflags stays sticky: flags are ORed in; status
+ *   is the last step's call); adopt_step [B][n] i32 in/out: the global step
+ *   of the vehicle's last adoption, -1 if none; vflags_hist [steps][B][n] i32
+ *   (optional): the ACL_FLEET_V_* raised during step k; fst [B]
+ *   acl_fleet_episode_status_t in/out (zeroed before step 0).
+ * workspace: acl_fleet_episode_workspace_bytes(n, B, queue_cap) bytes (the
+ * fleet workspace, the control hand-off region, the u / u_safe / ca scratch,
+ * the command buffer), zero-filled once by the caller and handed back
+ * unchanged with the same n, B, queue_cap. The first step of a call builds
+ * the control hand-off from the rows alone, so the caller may rewrite any
+ * state array between calls.
+ * A swarm with fidx out of range, or with a row that is not a permutation at
+ * the start of the call, is flagged ACL_FLEET_BAD_INPUT in fst and left
+ * untouched by the call: no ticks, no control, its state unchanged and its
+ * history rows not written (vflags_hist: 0). */
+typedef struct {
+  int32_t flags;       /* ACL_FLEET_BAD_INPUT (this call), ACL_FLEET_OVERFLOW (sticky) */
+  int32_t ticks_run;   /* accumulated */
+  int32_t n_started;   /* vehicle events, accumulated: START commands ... */
+  int32_t n_restarted; /* ... of which on an open auctioneer */
+  int32_t n_flushed;   /* FLUSH commands */
+  int32_t n_consensus; /* ACL_FLEET_V_CONSENSUS raised */
+  int32_t n_adopted;   /* ACL_FLEET_V_ADOPTED raised */
+  int32_t n_invalid;   /* ACL_FLEET_V_INVALID raised */
+} acl_fleet_episode_status_t; /* 32 bytes */
+
+typedef struct {
+  int32_t B;
+  int32_t step0;
+  int32_t steps;
+  int32_t ticks_per_step; /* >= 1 */
+  int32_t max_iter;       /* as acl_fleet_auction_args_t */
+  int32_t queue_cap;
+  const int32_t* fidx;    /* [B] */
+  double* q;              /* [B][n][3] */
+  double* vel;            /* [B][n][3] */
+  uint16_t* P;            /* [B][n] out: each vehicle's point in its own row */
+  uint16_t* Pt;           /* [B][n][n] ... the arrays of acl_fleet_auction_args_t */
+  uint8_t* open;
+  uint8_t* invalid;
+  uint8_t* just_received;
+  int32_t* biditer;
+  float* price;
+  int32_t* who;
+  double* Rt;
+  float* final_price;
+  int32_t* final_who;
+  int32_t* done_tick;
+  int32_t* vflags;
+  int32_t* n_thrown;
+  int32_t* n_tally;
+  int32_t* queue_len;
+  acl_fleet_status_t* status;
+  int32_t* adopt_step;    /* [B][n] in/out */
+  acl_episode_status_t* est;
+  double* ring_u;
+  uint8_t* ring_ca;
+  double* q_hist;         /* optional histories, as acl_episode_args_t */
+  double* vel_hist;
+  double* u_hist;
+  uint8_t* ca_hist;
+  uint16_t* P_hist;
+  int32_t* vflags_hist;   /* [steps][B][n] or NULL */
+  acl_fleet_episode_status_t* fst; /* [B] in/out */
+  void* workspace;
+  size_t workspace_bytes;
+  acl_cntrl_gains_t cntrl;
+  acl_safety_params_t safety;
+  acl_episode_params_t ep;
+} acl_fleet_episode_args_t;
+
+size_t acl_fleet_episode_workspace_bytes(int32_t n, int32_t B, int32_t queue_cap);
+acl_status_t acl_fleet_episode_batch(const acl_formations_t* formations,
+                                     const acl_fleet_episode_args_t* args, void* stream);
+
 /* ---- batched Monte-Carlo trials (ABI 9; SURVEY §8f widening of row f1) ---
  * B independent trials of aclswarm_sim's supervisor (aclswarm_sim/nodes/
  * supervisor.py:160-236) over the closed loop of acl_episode_batch: each

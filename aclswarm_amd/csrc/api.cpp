@@ -8,6 +8,7 @@
 #include <string>
 
 #include "../../include/aclswarm_amd.h"
+#include "neighbourhood_dev.h"
 
 namespace {
 thread_local std::string g_last_error;
@@ -253,3 +254,24 @@ extern "C" acl_status_t acl_stream_synchronize(void* stream) {
 }
 
 extern "C" int32_t acl_abi_version(void) { return ACL_ABI_VERSION; }
+
+// ---- test hooks ------------------------------------------------------------
+
+// The auction kernel's neighbourhood masks (neighbourhood_dev.h) for B swarms
+// on device data: adj [B][n][ceil(n / 64)] packed rows (acl_pack_adjacency),
+// P_in [B][n] i32 permutations, out [B][n][2] u64. mode: 0 automatic, 1 the
+// bit walk, 2 the ballot loop (tests/test_gpu_neighbourhoods.py). 0 on success.
+extern "C" int acl_internal_neighbourhoods(int n, int B, const uint64_t* adj, const int32_t* P_in,
+                                           unsigned long long* out, int mode) {
+  using namespace acl_amd;
+  if (n < 1 || n > 128 || B < 0 || mode < NB_AUTO || mode > NB_BALLOT) return 2;
+  if (B == 0) return 0;
+  if (n <= 32)
+    hipLaunchKernelGGL((neighbourhoods_kernel<1, 128>), dim3(B), dim3(128), 0, 0, n, adj, P_in, out, mode);
+  else if (n <= 64)
+    hipLaunchKernelGGL((neighbourhoods_kernel<1, 256>), dim3(B), dim3(256), 0, 0, n, adj, P_in, out, mode);
+  else
+    hipLaunchKernelGGL((neighbourhoods_kernel<2, 512>), dim3(B), dim3(512), 0, 0, n, adj, P_in, out, mode);
+  if (hipGetLastError() != hipSuccess) return 1;
+  return hipDeviceSynchronize() == hipSuccess ? 0 : 1;
+}

@@ -5,7 +5,9 @@
 // swarms per CU -- 53 KiB did not fit three after allocation rounding):
 //
 //   phase 0  load p, the adjacency bits, P_in (permutation check), q in
-//            formation order; vehicle-space closed neighbourhoods and their
+//            formation order; vehicle-space closed neighbourhoods (a bit walk
+//            per vehicle over its row's present or missing neighbours, or the
+//            ballot loop where a row's walk is long: neighbourhood_dev.h) and
 //            the alignment work list
 //   phase 1  2-D Umeyama alignment (Auctioneer::alignFormation,
 //            auctioneer.cpp:347-415). A vehicle's alignment depends only on
@@ -45,6 +47,7 @@
 #include "common.h"
 #include "control_dev.h"
 #include "control_params.h"
+#include "neighbourhood_dev.h"
 #include "pair_fused.h"
 #include "umeyama_dev.h"
 
@@ -778,6 +781,9 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
       }
     }
   }
+  // which build of the neighbourhood masks the swarm takes (below): adjF is
+  // complete since the barrier above, the vote is published by the next
+  if (!rowsm) nb_walk_vote<NC>(n, adjF, tid, lane, &misc[M_NBLONG]);
   __syncthreads();
   // (M_BAD is final here: the own-row checks below report into M_ROWBAD, so
   // no wave's entry test sees another wave's write and the barrier inside
@@ -830,24 +836,12 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
   }
   // closed neighbourhoods in vehicle space (bidIterComplete, auctioneer.cpp:
   // 419-437): u ~ v iff u == v or adj(P[v], P[u]) (rows: built above)
-  if (!rowsm) {
-    int pu[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) pu[c] = (lane + 64 * c < n) ? Pin[lane + 64 * c] : 0;
-    for (int v = wave; v < n; v += kAW) {
-      const int i = Pin[v];
-      const unsigned long long r0 = adjF[2 * i], r1 = adjF[2 * i + 1];
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int u = lane + 64 * c;
-        const bool okl = u < n;
-        const bool e = okl && (u == v || (((pu[c] < 64 ? r0 : r1) >> (pu[c] & 63)) & 1ull));
-        const unsigned long long me = __ballot(e);
-        if (lane == 0) vadj[2 * v + c] = me;
-      }
-      if (NC == 1 && lane == 0) vadj[2 * v + 1] = 0ull;
-    }
-  }
+  // Thread v walks the (missing) neighbours of its row; swarms with a row
+  // whose walk is long (M_NBLONG, voted between the barriers above) keep the
+  // one-wave-iteration-per-vehicle ballot loop (neighbourhood_dev.h).
+  if (!rowsm)
+    build_neighbourhoods<NC, kAB>(n, adjF, Pin, Ptin, vadj, tid, lane,
+                                  __builtin_amdgcn_readfirstlane(misc[M_NBLONG]) == 0);
   if (kInlineAlign && wave == 0 && !rowsm) {
     const int ni = align_worklist<NC>(n, adjF, items, itm, lane);
     if (lane == 0) misc[A_NITEMS] = ni;

@@ -182,7 +182,9 @@ struct SolveParams {
 enum { M_BAD = 0, M_NONFIN = 1, M_NINV = 5, M_AGREE = 6, M_CHANGED = 7, M_NCA = 8,
        M_PINF = 9 /* a formation coordinate is not finite */,
        M_MARG = 10 /* u64: bits of the swarm's minimum decision gap (misc[10..11]) */,
-       M_ROWBAD = 12 /* a vehicle's own row (P_rows) failed its check */ };
+       M_ROWBAD = 12 /* a vehicle's own row (P_rows) failed its check */,
+       M_NBLONG = 13 /* a formation row's bit walk is long: the ballot loop builds the
+                        neighbourhood masks (neighbourhood_dev.h; auction.hip only) */ };
 
 // Control stage: which = 0 launches the gain kernel for swarms
 // [P.b0, P.b0 + nb) (DistCntrl::compute, saturation, the collision test),

@@ -28,6 +28,11 @@
 //     (14 vector instructions per tile instead of 36), then one ds_add_f64
 //     per (column, component) lane into the wave's own accumulator (one
 //     writer per address and instruction, in program order: deterministic);
+//   * where the last column block holds only 1 to 4 real columns (n mod 8)
+//     and there are at least three row blocks, its off-diagonal tiles run two
+//     to a tile after the regular ones (lanes c < 4 one row block, c >= 4 the
+//     next: 91 -> 85 tiles at n = 100); the regular tile body is unchanged and
+//     the diagonal tiles are not folded;
 //   * the first collision test's candidate search from the pair loop's own q
 //     differences: a conservative test (the squared xy distance, contracted,
 //     against (thr (1 + 2^-40))^2) flags the formation rows that need the
@@ -51,6 +56,10 @@
 #endif
 #ifndef ACL_DIAG_NOLOOP
 #define ACL_DIAG_NOLOOP 0
+#endif
+// 0: every tile of the upper triangle runs unpacked (A/B builds)
+#ifndef ACL_FUSED_PACK
+#define ACL_FUSED_PACK 1
 #endif
 
 namespace acl_amd {
@@ -335,16 +344,28 @@ __device__ __forceinline__ void pair_gain_fused(KCtlParams* Pp, int b, int f,
     const int r = lane >> 3, c = lane & 7;
     // the lane's (column, component) slot of the packed column sums
     const int colk = 3 * c + ((lane >> 4) == 0 ? 0 : ((lane >> 4) == 1 ? 2 : 1));
-    const int NT = nb * (nb + 1) / 2;
+    // Packed edge tiles: where the last column block holds 1 to 4 real columns
+    // (n mod 8) its nb - 1 off-diagonal tiles run half empty, so two of them,
+    // (I, nb - 1) and (I + 1, nb - 1), share one tile (lanes c < 4 / c >= 4).
+    // They leave the regular order (a row block then ends at column block
+    // nb - 2) and follow it as tiles NR .. NT - 1 with a loop of their own
+    // below; the per-wave split runs over all NT.
+    const bool pack = ACL_FUSED_PACK && (n & 7) >= 1 && (n & 7) <= 4 && nb >= 3;  // uniform
+    const int NR = nb * (nb + 1) / 2 - (pack ? nb - 1 : 0);
+    const int NT = NR + (pack ? nb >> 1 : 0);  // ceil((nb - 1) / 2) packed tiles
     const int t0 = (wave * NT) / kW, t1 = ACL_DIAG_NOLOOP ? t0 : ((wave + 1) * NT) / kW;
+    const int t1r = t1 < NR ? t1 : NR;  // the regular tiles of the range
     double* myacc = acc + wave * R * 3;
 
-    // tile t -> (I, J), J >= I, row block by row block
+    // tile t -> (I, J), J >= I, row block by row block (J < jl: the row
+    // block's end)
     int I = 0, J = 0;
-    if (t0 < t1) {
+    if (t0 < t1r) {
       int rem = t0;
-      while (rem >= nb - I) {
-        rem -= nb - I;
+      for (;;) {
+        const int len = ((pack && I < nb - 1) ? nb - 1 : nb) - I;
+        if (rem < len) break;
+        rem -= len;
         ++I;
       }
       J = I + rem;
@@ -368,7 +389,7 @@ __device__ __forceinline__ void pair_gain_fused(KCtlParams* Pp, int b, int f,
     };
     Rec5 X, Y;
     unsigned long long mx = 0ull, my = 0ull;
-    if (t0 < t1) {
+    if (t0 < t1r) {
       const unsigned xij = etab[__umul24(8 * I + r, nb) + J], xji = etab[__umul24(8 * J + c, nb) + I];
       mx = rec_mask(xij, c, I == J, kTileUpIncl);
       my = rec_mask(xji, r, I == J, kTileUpStrict);
@@ -377,14 +398,14 @@ __device__ __forceinline__ void pair_gain_fused(KCtlParams* Pp, int b, int f,
     }
     double ra0 = 0.0, ra1 = 0.0, ra2 = 0.0;  // row sums of the current row block
 #pragma unroll 1
-    for (int t = t0; t < t1; ++t) {
+    for (int t = t0; t < t1r; ++t) {
 #pragma clang fp contract(fast)
       int In = I, Jn = J;  // the next tile
-      if (++Jn == nb) {
+      if (++Jn == ((pack && I < nb - 1) ? nb - 1 : nb)) {
         ++In;
         Jn = In;
       }
-      const bool more = t + 1 < t1;  // wave-uniform
+      const bool more = t + 1 < t1r;  // wave-uniform
       // the next tile's etab words, read early (their latency hides here)
       unsigned xijn = 0u, xjin = 0u;
       if (more) {
@@ -488,6 +509,104 @@ __device__ __forceinline__ void pair_gain_fused(KCtlParams* Pp, int b, int f,
       J = Jn;
       mx = mxn;
       my = myn;
+    }
+    // ---- the packed edge tiles of the range. Lane (r, c): row block
+    // Ih = Ip + (c >> 2), i = 8 Ih + r, column j = 8 (nb - 1) + (c & 3). The
+    // record of (i, j) is bit c & 3 of row i's last etab word, that of (j, i)
+    // bit r of row j's word of block Ih. An odd tile out (Ip + 1 = nb - 1, the
+    // diagonal block) runs with its upper half masked. Every tile has row
+    // blocks of its own, so the row sums (over the 4 lanes of a half: two
+    // DPP steps) are flushed per tile; the column sums of c and c + 4 belong
+    // to one column and are combined by one more DPP step (row_ror 4: lanes
+    // 8-15 of a row mirror lanes 0-7 after col3_neg), lanes c < 4 write.
+#pragma unroll 1
+    for (int t = t0 > NR ? t0 : NR; t < t1; ++t) {
+#pragma clang fp contract(fast)
+      const int Ip = 2 * (t - NR);
+      const bool two = Ip + 1 < nb - 1;  // wave-uniform
+      const unsigned long long hm = two ? ~0ull : 0x0F0F0F0F0F0F0F0Full;
+      const int h = c >> 2, cc = c & 3, Ih = Ip + h;
+      const int i = 8 * Ih + r, j = 8 * (nb - 1) + cc;
+      const unsigned xij = etab[__umul24(i, nb) + (nb - 1)], xji = etab[__umul24(j, nb) + Ih];
+      const unsigned long long pmx = __ballot((xij >> cc) & 1u) & hm;
+      const unsigned long long pmy = __ballot((xji >> r) & 1u) & hm;
+      rec_load(xij, cc, pmx, X);
+      rec_load(xji, r, pmy, Y);
+      const double4* pi = reinterpret_cast<const double4*>(pt + 8 * i);
+      const double4* pj = reinterpret_cast<const double4*>(pt + 8 * j);
+      const double4 ai = pi[0], aj = pj[0];  // {q.x, q.y, q.z, p.x}
+      const double q0 = aj.x - ai.x, q1 = aj.y - ai.y, q2 = aj.z - ai.z;
+      const double s2 = pair_s2(q0, q1);
+      {
+        // collision candidates: the real columns of both halves (every row of
+        // a live half is real: Ih <= nb - 2; i < j throughout)
+        const int nc = n - 8 * (nb - 1);  // 1 .. 4
+        const unsigned long long vm = (((1ull << nc) - 1ull) * 0x1111111111111111ull) & hm;
+        const unsigned long long nm = __ballot(!(s2 > fcst(cst, FC_THR2))) & vm;
+        if (nm) {
+          if (lanebit_u64(nm)) {
+            atomicOr(&nearb[i >> 5], 1u << (i & 31));
+            atomicOr(&nearb[j >> 5], 1u << (j & 31));
+          }
+        }
+      }
+      double Fxy = 0.0, Fz = 0.0;
+      if (!ACL_DIAG_NOPAIR && lanebit_u64(pmx | pmy)) {
+        const double4 bi = pi[1], bj = pj[1];  // {p.y, p.z, pn_xy, pn_z}
+        const double pix = ai.w, piy = bi.x, piz = bi.y, pjx = aj.w, pjy = bj.x, pjz = bj.y;
+        double e_xy, e_z;
+        pair_e(q0, q1, q2, bi.z, bj.z, bi.w, bj.w, pix, piy, piz, pjx, pjy, pjz, s2, e_xy, e_z);
+        bool gxy, gz;
+        gate_decide_t<GM>(fcst(cst, FC_TXY), fcst(cst, FC_TZ), fcst(cst, FC_WIN), e_xy, e_z, q0,
+                          q1, q2, bi.z, bj.z, bi.w, bj.w, pix, piy, piz, pjx, pjy, pjz, gxy, gz,
+                          gmxy, gmz);
+#if ACL_DIAG_NOATAN
+        if (gxy) Fxy = fcst(cst, FC_K1XY) * (fcst(cst, FC_K2XY) * e_xy);
+        if (gz) Fz = fcst(cst, FC_K1Z) * (fcst(cst, FC_K2Z) * e_z);
+#else
+        if (gxy) Fxy = fcst(cst, FC_K1XY) * ACL_GAIN_ATAN(fcst(cst, FC_K2XY) * e_xy, atab);
+        if (gz) Fz = fcst(cst, FC_K1Z) * ACL_GAIN_ATAN(fcst(cst, FC_K2Z) * e_z, atab);
+#endif
+      }
+      const double f0 = Fxy * q0, f1 = Fxy * q1, f2 = Fz * q2;
+      double pa0 = 0.0, pa1 = 0.0, pa2 = 0.0;
+      if (lanebit_u64(pmx)) {
+        if (qfin) {
+          pa0 = X.a[1] * q1 + (X.a[0] * q0 + f0);
+          pa1 = X.a[3] * q1 + (X.a[2] * q0 + f1);
+          pa2 = X.a[4] * q2 + f2;
+        } else {
+          pa0 = ((X.a[0] * q0 + X.a[1] * q1) + 0.0 * q2) + f0;
+          pa1 = ((X.a[2] * q0 + X.a[3] * q1) + 0.0 * q2) + f1;
+          pa2 = ((0.0 * q0 + 0.0 * q1) + X.a[4] * q2) + f2;
+        }
+      }
+      double ct0 = 0.0, ct1 = 0.0, ct2 = 0.0;
+      if (lanebit_u64(pmy)) {
+        if (qfin) {
+          ct0 = Y.a[1] * q1 + (Y.a[0] * q0 + f0);
+          ct1 = Y.a[3] * q1 + (Y.a[2] * q0 + f1);
+          ct2 = Y.a[4] * q2 + f2;
+        } else {
+          ct0 = ((Y.a[0] * q0 + Y.a[1] * q1) + 0.0 * q2) + f0;
+          ct1 = ((Y.a[2] * q0 + Y.a[3] * q1) + 0.0 * q2) + f1;
+          ct2 = ((0.0 * q0 + 0.0 * q1) + Y.a[4] * q2) + f2;
+        }
+      }
+      {
+        double cs = col3_neg(ct0, ct1, ct2);
+        cs += dpp_f64_all<0x124>(cs);
+        if (lanebit_u64(kColLanes & 0x0F0F0F0F0F0F0F0Full))
+          unsafeAtomicAdd(myacc + 24 * (nb - 1) + colk, cs);
+      }
+      pa0 += dpp_f64_all<0xB1>(pa0); pa1 += dpp_f64_all<0xB1>(pa1); pa2 += dpp_f64_all<0xB1>(pa2);
+      pa0 += dpp_f64_all<0x4E>(pa0); pa1 += dpp_f64_all<0x4E>(pa1); pa2 += dpp_f64_all<0x4E>(pa2);
+      if (cc == 0 && (two || h == 0)) {
+        double* a = myacc + 3 * i;
+        unsafeAtomicAdd(a, pa0);
+        unsafeAtomicAdd(a + 1, pa1);
+        unsafeAtomicAdd(a + 2, pa2);
+      }
     }
     if (GM) {
       const acl_cntrl_gains_t g = kgains(P);

@@ -387,6 +387,20 @@ __device__ __forceinline__ void level_hits(const unsigned long long (&open)[NC],
   }
 }
 
+// the same with every real vehicle open (a lane past n has empty masks)
+template <int NC>
+__device__ __forceinline__ void level_hits_all(const unsigned long long (&h)[NC],
+                                               const unsigned long long (&vm)[NC][NC],
+                                               unsigned long long (&hitm)[NC]) {
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    unsigned long long t = 0ull;
+#pragma unroll
+    for (int w = 0; w < NC; ++w) t |= vm[c][w] & h[w];
+    hitm[c] = __ballot(t != 0ull);
+  }
+}
+
 // The exact decision gaps of a column's level-resolved vehicles (k1 != 0):
 // walk the levels again; a vehicle's runner-up is the first level below its
 // winning level that its neighbourhood holds. The largest ratio among the
@@ -953,7 +967,9 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
     for (int w = 0; w < NC; ++w) vm[c][w] = (v < n) ? vadj[2 * v + w] : 0ull;
   }
   __syncthreads();  // region A (p, qf, out) is dead from here: T overlays it
-  const bool nonfinite = misc[M_NONFIN] != 0;
+  // (workgroup-uniform: read through the scalar unit, so the tests on it are scalar branches)
+  const bool nonfinite = __builtin_amdgcn_readfirstlane(misc[M_NONFIN]) != 0;
+  const unsigned long long nfm = nonfinite ? ~0ull : 0ull;  // as a lane mask
   stamp_phase(P, b, tid, 3);
   ACL_AUCTION_STOP_AT(3);
 
@@ -1066,18 +1082,16 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
     };
     float Gfacf = gfac(Gw);
     {
-      // one loop over both words (the column body is emitted once)
-      unsigned long long mm = mine[0], m1 = NC > 1 ? mine[NC - 1] : 0ull;
-      int jb = 0;
-      for (;;) {
-        if (!mm) {
-          if (!m1) break;
-          mm = m1;
-          m1 = 0ull;
-          jb = 64;
-        }
-        const int j = jb + __ffsll((long long)mm) - 1;
-        mm &= mm - 1;
+      // word by word (the column body is emitted once): which word the next
+      // bit comes from is decided once per word, not per column
+#pragma unroll 1
+      for (int jw = 0; jw < NC; ++jw) {
+      const int jb = 64 * jw;
+      const unsigned dbit = 1u << (FL_DIRTY + jw);  // the word's dirty flag
+#pragma unroll 1
+      for (unsigned long long mm = jw ? mine[NC - 1] : mine[0]; mm; mm &= mm - 1) {
+        const int jl = __ffsll((long long)mm) - 1;
+        const int j = jb + jl;
         // one wave per dirty column, lanes = vehicles
         int wu[NC], nw[NC];
         unsigned key[NC];
@@ -1097,7 +1111,7 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
           h[c] = __ballot(key[c] == M0);
-          cum += __popcll(h[c]);
+          if (kMarg) cum += __popcll(h[c]);
         }
         int wk = first_who<NC>(h, wu);
         unsigned long long tie = 0ull;
@@ -1116,57 +1130,49 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
         // so the test cost more than it saved; the levels resolve it exactly)
         sp.mark(PS_L0);
         // winners, level by level. Per-vehicle state as lane masks: U = not
-        // yet resolved, Nd = exact scan. Each resolving level's successor
-        // bounds the decision gap of the vehicles it resolved (their
-        // runner-up is that level or a lower one).
-        unsigned long long U[NC], Nd[NC];
+        // yet resolved; whoever is left in U after the levels takes the exact
+        // scan. Each resolving level's successor bounds the decision gap of
+        // the vehicles it resolved (their runner-up is that level or a lower
+        // one).
+        unsigned long long U[NC];
         unsigned k1[NC];  // a vehicle's winning level key (0: tie / scan)
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          U[c] = okm[c];
-          Nd[c] = 0ull;
-          k1[c] = 0u;
-        }
-        unsigned Mk = M0, kres = 0u;  // kres: the last level that resolved a vehicle
+        unsigned kres = 0u;  // the last level that resolved a vehicle
         // the runner-up walk is needed: a resolving level's successor within
         // Gw (its vehicles' decision gaps are at least that level pair's)
         bool walk = false;
-        if (nonfinite) {  // NaN prices: the exact scan for every vehicle
+        // Level 0, peeled: straight-line code for the common column, which it
+        // resolves whole. NaN prices, and a level held under two `who`s
+        // (equal prices), resolve nobody here (`keep` clears the hits) and
+        // leave every vehicle to the exact scan.
+        const unsigned long long blk = tie | nfm;
+        const unsigned long long keep = blk ? 0ull : ~0ull;
+        unsigned long long left = 0ull;  // vehicles left for the exact scan (any bit)
+        {
+          unsigned long long hitm[NC], res = 0ull;
+          // (every real vehicle is open: the neighbourhood mask of a lane
+          // past n is empty, so the hits need no mask)
+          level_hits_all<NC>(h, vm, hitm);
 #pragma unroll
           for (int c = 0; c < NC; ++c) {
-            Nd[c] = U[c];
-            U[c] = 0ull;
+            hitm[c] &= keep;
+            const bool hit = lanebit(hitm[c]);
+            nw[c] = hit ? wk : nw[c];
+            if (kMarg) k1[c] = hit ? M0 : 0u;
+            U[c] = okm[c] & ~hitm[c];
+            left |= U[c];
+            res |= hitm[c];
           }
-        } else {
+          if (kMarg) kres = res ? M0 : 0u;
+        }
+        // Levels 1 to kAL - 1, one exit: a tie resolves nobody and ends the
+        // loop (rare; the bound of the last resolving level was taken against
+        // this level), so the loop carries U, the level key and the counter.
+        if (kAL > 1 && left && !blk) {
+          bool more;
+          unsigned Mk = M0;
+          int k = 1;
 #pragma unroll 1
-          for (int k = 0;;) {
-            if (tie) {
-              // a level held under two `who`s (equal prices): the exact scan
-              // for every vehicle not resolved above it (rare; the bound of
-              // the last resolving level was taken against this level)
-#pragma unroll
-              for (int c = 0; c < NC; ++c) {
-                Nd[c] = U[c];
-                U[c] = 0ull;
-              }
-              kres = 0u;
-              break;
-            }
-            unsigned long long hitm[NC];
-            level_hits<NC>(U, h, vm, hitm);
-            unsigned long long left = 0ull, res = 0ull;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-              const bool hit = lanebit(hitm[c]);
-              nw[c] = hit ? wk : nw[c];
-              k1[c] = hit ? Mk : k1[c];
-              U[c] &= ~hitm[c];
-              left |= U[c];
-              res |= hitm[c];
-            }
-            kres = res ? Mk : 0u;
-            if (!left || ++k == kAL) break;
-            // the next level
+          do {
             Mk = level_key<NC>(key, Mk);
             if (kMarg) {
               // gap(P(kres), P(Mk)) <= Gw, tested conservatively in f32
@@ -1177,13 +1183,28 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
               h[c] = __ballot(key[c] == Mk);
-              cum += __popcll(h[c]);
+              if (kMarg) cum += __popcll(h[c]);
             }
             wk = first_who<NC>(h, wu);
             tie = 0ull;
 #pragma unroll
             for (int c = 0; c < NC; ++c) tie |= h[c] & __ballot(wu[c] != wk);
-          }
+            unsigned long long hitm[NC], res = 0ull;
+            level_hits<NC>(U, h, vm, hitm);
+            left = 0ull;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+              hitm[c] = tie ? 0ull : hitm[c];
+              const bool hit = lanebit(hitm[c]);
+              nw[c] = hit ? wk : nw[c];
+              if (kMarg) k1[c] = hit ? Mk : k1[c];
+              U[c] &= ~hitm[c];
+              left |= U[c];
+              res |= hitm[c];
+            }
+            if (kMarg) kres = res ? Mk : 0u;
+            more = !tie && left != 0ull && ++k < kAL;
+          } while (more);
         }
         sp.mark(PS_LV);
         if (kMarg && !walk && kres != 0u && cum < n) {
@@ -1206,7 +1227,8 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
         walk = walk && kMarg;
         sp.mark(PS_MB);
         if (walk) {
-          runner_up_walk<NC>(n, key, k1, Nd, vm, uhi, ulo);
+          // (a vehicle still in U was never hit: its k1 is 0)
+          runner_up_walk<NC>(n, key, k1, U, vm, uhi, ulo);
           Gw = fmin(Gpub, margin_gap_pair(uhi, ulo));
           Gwf = (float)(Gw * (1.0 + 0x1p-20));
           Gfacf = gfac(Gw);
@@ -1216,17 +1238,11 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
         // the exact ordered scan (ascending vehid, strict >) for ties, NaN
         // prices and vehicles the levels did not resolve; the runner-up is the
         // best price of another `who` (entries of one `who` share its price)
-        unsigned long long scan = 0ull;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          Nd[c] |= U[c];
-          scan |= Nd[c];
-        }
-        if (scan) {
+        if (left) {
           if (ACL_AUCTION_PROF) sp.scans++;
 #pragma unroll
           for (int c = 0; c < NC; ++c) {
-            if (lanebit(Nd[c])) {
+            if (lanebit(U[c])) {
               float bp = 0.0f, p2 = 0.0f;
               int bw = n;
               bool first = true, have2 = false;
@@ -1263,20 +1279,24 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
         for (int c = 0; c < NC; ++c) {
           // (lanes past n store to a dummy row: no branch, see margin_track_sel)
           smem[okv[c] ? L.T + rowa[c] + j : L.dummy + lane] = (unsigned char)nw[c];
-          const int u = lane + 64 * c;
-          fl |= (vflag(okv[c]) & vflag(wu[c] == u) & vflag(nw[c] != u)) << c;
-          ch |= __ballot(nw[c] != wu[c]);
-          mixed |= __ballot(okv[c] && nw[c] != nw0);
+          // outbid: the vehicle held its own entry and lost it (a lane past n
+          // keeps its entry: it is never hit and never scanned)
+          const bool chg = nw[c] != wu[c];
+          fl |= (chg && wu[c] == lane + 64 * c) ? 1u << c : 0u;
+          ch |= __ballot(chg);
+          mixed |= __ballot(nw[c] != nw0) & okm[c];
         }
         // A column left holding one `who` everywhere is a fixed point (every
         // neighbourhood sees one (price, who)) with no runner-up: it is not
         // dirty next round unless a re-select writes it (which marks it).
         // The change itself still counts for eff_rounds.
-        if (ch) {
-          fl |= 1u << FL_CH;
-          if (mixed || nonfinite) fl |= vflag(lane == (j & 63)) << (FL_DIRTY + (j >> 6));
-        }
+        // (branch-free: the flags straight from the masks)
+        const bool chb = ch != 0ull;
+        const bool dirty = chb && (mixed != 0ull || nonfinite);
+        fl |= chb ? 1u << FL_CH : 0u;
+        fl |= lane == (dirty ? jl : 64) ? dbit : 0u;
         sp.mark(PS_WB);
+      }
       }
     }
     }  // (a wave with no dirty column)

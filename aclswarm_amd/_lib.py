@@ -41,6 +41,7 @@ EXPORTS = (
     "acl_fleet_episode_workspace_bytes", "acl_fleet_episode_batch",
     "acl_default_episode_params", "acl_episode_workspace_bytes", "acl_episode_batch",
     "acl_default_trial_params", "acl_trial_workspace_bytes", "acl_trial_init", "acl_trial_batch",
+    "acl_fleet_trial_workspace_bytes", "acl_fleet_trial_init", "acl_fleet_trial_batch",
     "acl_generate_formation_groups",
     "acl_malloc", "acl_free", "acl_memcpy_h2d", "acl_memcpy_d2h", "acl_memset",
     "acl_stream_synchronize", "acl_last_error",
@@ -227,6 +228,21 @@ class TrialArgs(ct.Structure):
         ("cntrl", CntrlGains), ("safety", SafetyParams), ("tp", TrialParams)]
 
 
+class FleetTrialArgs(ct.Structure):
+    """acl_fleet_trial_args_t (added within ABI 11): trials on the message-level
+    auction."""
+    _fields_ = [(k, ct.c_int32) for k in ("B", "K", "step0", "steps", "ticks_per_step",
+                                          "max_iter", "queue_cap")] + [
+        (k, ct.c_void_p) for k in (
+            "fseq", "fidx", "q", "vel", "P", "ts", "ctl_on", "ring_u", "ring_ca", "posf", "dist",
+            "t_conv", "t_avoid", "n_assign", "Pt", "open", "invalid", "just_received", "biditer",
+            "price", "who", "Rt", "final_price", "final_who", "done_tick", "vflags", "n_thrown",
+            "n_tally", "queue_len", "status", "adopt_step", "fst", "q_hist", "vel_hist", "u_hist",
+            "ca_hist", "ctl_hist", "P_hist", "state_hist", "vflags_hist", "workspace")] + [
+        ("workspace_bytes", ct.c_size_t), ("cntrl", CntrlGains), ("safety", SafetyParams),
+        ("tp", TrialParams)]
+
+
 HUNG_BAD_INPUT = 0x01
 HUNG_NONFINITE = 0x02
 HUNG_CMP_INVALID = 0x04
@@ -296,6 +312,12 @@ def lib():
     L.acl_trial_init.restype = ct.c_int
     L.acl_trial_batch.argtypes = [ct.POINTER(Formations), ct.POINTER(TrialArgs), VP]
     L.acl_trial_batch.restype = ct.c_int
+    L.acl_fleet_trial_workspace_bytes.argtypes = [I32, I32, I32]
+    L.acl_fleet_trial_workspace_bytes.restype = SZ
+    L.acl_fleet_trial_init.argtypes = [ct.POINTER(FleetTrialArgs), I32, VP]
+    L.acl_fleet_trial_init.restype = ct.c_int
+    L.acl_fleet_trial_batch.argtypes = [ct.POINTER(Formations), ct.POINTER(FleetTrialArgs), VP]
+    L.acl_fleet_trial_batch.restype = ct.c_int
     L.acl_generate_formation_groups.argtypes = [I32, I32, VP, I32, ct.c_double, ct.c_double,
                                                 ct.c_double, ct.c_double, I64, VP, VP, VP,
                                                 VP, VP]

@@ -33,6 +33,7 @@
 // that resets a table with a bid still in flight copies it aside first.
 #include "common.h"
 #include "cbaa_select_dev.h"  // step_select
+#include "fleet_dev.h"        // FleetMeta, fleet_layout, role_phys, the table helpers
 #include "own_row_dev.h"      // own_row_check, own_row_align
 
 #include "../../include/aclswarm_amd.h"
@@ -49,39 +50,6 @@ template <int S>
 struct FleetWaves {
   static constexpr int value = S == 1 ? 4 : 16;
 };
-constexpr int kFleetMaxN = 128;
-
-// per-vehicle bookkeeping kept in the workspace between calls (all zero: a
-// freshly constructed auctioneer)
-struct FleetMeta {
-  unsigned long long mz[2], mc[2], mn[2];  // senders present in START / current / next
-  int qhead, qlen;                         // the queue ring
-  int live, live_iter;    // a bid in flight that is the vehicle's own table
-  int stale, stale_iter;  // one in flight from before a command reset the table
-  int roles;              // physical bucket of role r: ((roles >> 2r) & 3) ^ r
-  int pad;
-};
-static_assert(sizeof(FleetMeta) == 80, "FleetMeta layout");
-
-enum { kRoleZero = 0, kRoleCurr = 1, kRoleNext = 2 };
-
-struct FleetLayout {
-  size_t meta, qv, stale, bucket, queue, total;
-};
-
-// per-swarm workspace: [tick i32, pad][meta n][start position n x 3 f64]
-// [stale table n][buckets n x 3 x n tables][queues n x cap entries]
-__host__ __device__ inline FleetLayout fleet_layout(int n, int cap) {
-  const size_t N = (size_t)n, tb = 8 * N;  // a table: price f32[n], who i32[n]
-  FleetLayout L;
-  L.meta = 16;
-  L.qv = L.meta + N * sizeof(FleetMeta);
-  L.stale = L.qv + N * 24;
-  L.bucket = L.stale + N * tb;
-  L.queue = L.bucket + N * 3 * N * tb;
-  L.total = L.queue + N * (size_t)cap * (8 + tb);
-  return L;
-}
 
 struct FleetParams {
   int n, B, F, ticks, max_iter, cap;
@@ -110,18 +78,6 @@ struct FleetParams {
   uint8_t* hist_open;
   unsigned char* ws;
 };
-
-// (clamped: a workspace that was not zero-filled must not index past the buckets)
-__device__ __forceinline__ int role_phys(int roles, int r) {
-  const int ph = ((roles >> (2 * r)) & 3) ^ r;
-  return ph > 2 ? 2 : ph;
-}
-
-__device__ __forceinline__ int roles_swap(int roles, int a, int b) {
-  const int pa = role_phys(roles, a), pb = role_phys(roles, b);
-  roles &= ~((3 << (2 * a)) | (3 << (2 * b)));
-  return roles | ((pb ^ a) << (2 * a)) | ((pa ^ b) << (2 * b));
-}
 
 __device__ __forceinline__ bool mask_has(const unsigned long long (&m)[2], int u) {
   return (((u >> 6) ? m[1] : m[0]) >> (u & 63)) & 1ull;
@@ -165,32 +121,6 @@ __device__ __forceinline__ void fleet_sub_mask(const unsigned long long* adjrow,
   }
   sub[0] = ((unsigned long long)w1 << 32) | w0;
   sub[1] = ((unsigned long long)w3 << 32) | w2;
-}
-
-// reset() (auctioneer.cpp:448-465) of the table in memory
-template <int S>
-__device__ __forceinline__ void fleet_clear_table(float* pr, int32_t* wh, int n, int lane) {
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    const int j = lane + 64 * s;
-    if (j < n) {
-      pr[j] = 0.0f;
-      wh[j] = -1;
-    }
-  }
-}
-
-template <int S>
-__device__ __forceinline__ void fleet_copy_table(float* dp, int32_t* dw, const float* sp,
-                                                 const int32_t* sw, int n, int lane) {
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    const int j = lane + 64 * s;
-    if (j < n) {
-      dp[j] = sp[j];
-      dw[j] = sw[j];
-    }
-  }
 }
 
 template <int S>

@@ -980,6 +980,165 @@ class Trial:
                 "done_step": st["done_step"].copy()}
 
 
+class FleetTrial:
+    """Monte-Carlo trials on the message-level auction (acl_fleet_trial_batch,
+    added within ABI 11): Trial's supervisor, formation sequence and
+    controller starts over FleetAuction's per-vehicle auctioneers, B swarms of
+    n <= 128 vehicles. A formation change interrupts the auction in flight,
+    every vehicle adopts and starts its controller on its own, and the
+    supervisor hears vehicle 0 only. include/aclswarm_amd.h states the model
+    and its limits.
+
+    fseq [B][K] int32, q/vel [B][n][3] f64 on the table's device (copied).
+    queue_cap None: 4 n; max_iter 0: 2 n. The object owns the state: Trial's
+    (q, vel, P, ts, ctl_on, the rings, posf and the records), FleetEpisode's
+    fleet state, outputs, adopt_step and fst. Raises ValueError on a malformed
+    argument before anything is allocated."""
+
+    TRIAL_KEYS = ("fseq", "fidx", "q", "vel", "P", "ts", "ctl_on", "ring_u", "ring_ca", "posf",
+                  "dist", "t_conv", "t_avoid", "n_assign")
+    FLEET_KEYS = FleetEpisode.FLEET_KEYS + ("adopt_step", "fst")
+
+    def __init__(self, table, fseq, q, vel, params=None, cntrl=None, safety=None, queue_cap=None,
+                 max_iter=0, ticks_per_step=10):
+        n = table.n
+        if n < 1 or n > L.FLEET_MAX_N:
+            raise ValueError(f"FleetTrial: n = {n} out of range [1, {L.FLEET_MAX_N}]")
+        if not isinstance(q, torch.Tensor) or q.dim() != 3:
+            raise ValueError(f"FleetTrial: q must be a torch.float64 tensor of shape [B][{n}][3]")
+        B = int(q.shape[0])
+        if B < 1:
+            raise ValueError("FleetTrial: q is empty")
+        if queue_cap is None:
+            queue_cap = 4 * n
+        if int(queue_cap) < 1:
+            raise ValueError(f"FleetTrial: queue_cap = {queue_cap} < 1")
+        if int(max_iter) < 0:
+            raise ValueError(f"FleetTrial: max_iter = {max_iter} < 0")
+        if int(ticks_per_step) < 1:
+            raise ValueError(f"FleetTrial: ticks_per_step = {ticks_per_step} < 1")
+        if params is not None and (params.ep.auction_latency != 0 or params.ep.assignment != 0):
+            raise ValueError("FleetTrial: params.ep.auction_latency and params.ep.assignment must "
+                             "be 0 (the auction takes the time its messages take)")
+        _check_state("FleetTrial", table, {"q": (q, torch.float64, (B, n, 3)),
+                                           "vel": (vel, torch.float64, (B, n, 3)),
+                                           "fseq": (fseq, torch.int32, (B, None))})
+        dev = q.device
+        self.table, self.n, self.B, self.device = table, n, B, dev
+        self.K = K = int(fseq.shape[1])
+        self.queue_cap, self.max_iter = int(queue_cap), int(max_iter)
+        self.ticks_per_step = int(ticks_per_step)
+        self.tp = params or L.default_trial_params()
+        self.cntrl = cntrl or L.default_gains()
+        self.safety = safety or L.default_safety()
+        Lb = int(self.tp.ep.bufflen)
+        self.fseq = fseq
+        self.q = q.clone().contiguous()
+        self.vel = vel.clone().contiguous()
+
+        def e(shape, dt):
+            return torch.empty(shape, dtype=dt, device=dev)
+        # (every array below is set by acl_fleet_trial_init)
+        self.fidx = e((B,), torch.int32)
+        self.P = e((B, n), torch.int16)
+        self.ts = e((B, L.TRIAL_STATUS_DTYPE.itemsize), torch.uint8)
+        self.ctl_on = e((B, n), torch.uint8)
+        self.ring_u = e((B, Lb, n), torch.float64)
+        self.ring_ca = e((B, Lb, n), torch.uint8)
+        self.posf = e((B, 2, n), torch.float64)
+        self.dist = e((B, n), torch.float64)
+        self.t_conv = e((B, K), torch.float64)
+        self.t_avoid = e((B, K), torch.float64)
+        self.n_assign = e((B, K), torch.int32)
+        self.Pt = e((B, n, n), torch.int16)
+        self.open = e((B, n), torch.uint8)
+        self.invalid = e((B, n), torch.uint8)
+        self.just_received = e((B, n), torch.uint8)
+        self.biditer = e((B, n), torch.int32)
+        self.price = e((B, n, n), torch.float32)
+        self.who = e((B, n, n), torch.int32)
+        self.Rt = e((B, n, 6), torch.float64)
+        self.final_price = e((B, n, n), torch.float32)
+        self.final_who = e((B, n, n), torch.int32)
+        self.done_tick = e((B, n), torch.int32)
+        self.vflags = e((B, n), torch.int32)
+        self.n_thrown = e((B, n), torch.int32)
+        self.n_tally = e((B, n), torch.int32)
+        self.queue_len = e((B, n), torch.int32)
+        self.adopt_step = e((B, n), torch.int32)
+        self._status = e((B, 4), torch.int32)
+        self.fst = e((B, L.FLEET_EPISODE_STATUS_DTYPE.itemsize), torch.uint8)
+        self.ws = e((self.workspace_bytes(),), torch.uint8)
+        self.step = 0
+        a = self._args(0)
+        L.check(L.lib().acl_fleet_trial_init(ct.byref(a), n, ct.c_void_p(
+            torch.cuda.current_stream(dev).cuda_stream)), "acl_fleet_trial_init")
+
+    def workspace_bytes(self):
+        return int(L.lib().acl_fleet_trial_workspace_bytes(self.n, self.B, self.queue_cap))
+
+    def _args(self, steps, hist=None):
+        a = L.FleetTrialArgs()
+        a.B, a.K, a.step0, a.steps = self.B, self.K, self.step, steps
+        a.ticks_per_step, a.max_iter, a.queue_cap = self.ticks_per_step, self.max_iter, \
+            self.queue_cap
+        for k in self.TRIAL_KEYS + self.FLEET_KEYS:
+            setattr(a, k, getattr(self, k).data_ptr())
+        a.status = self._status.data_ptr()
+        if hist is not None:
+            for k, v in hist.items():
+                setattr(a, k + "_hist", v.data_ptr())
+        a.workspace = self.ws.data_ptr()
+        a.workspace_bytes = self.ws.numel()
+        a.cntrl, a.safety, a.tp = self.cntrl, self.safety, self.tp
+        return a
+
+    def run(self, steps, history=False, stream=None):
+        """Advance every trial `steps` control periods. With history=True
+        returns per-step device tensors q/vel/u [steps][B][n][3] (u: 0 for
+        stopped controllers), ca/ctl [steps][B][n], P [steps][B][n] (int16),
+        state [steps][B] and vflags [steps][B][n] i32 (the FLEET_V_* of _lib
+        raised during the step); rows of BAD_INPUT swarms stay 0; else None."""
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError(f"FleetTrial.run: steps = {steps} < 0")
+        dev, B, n = self.device, self.B, self.n
+        hist = None
+        if history:
+            def z(shape, dt):
+                return torch.zeros(shape, dtype=dt, device=dev)
+            hist = {"q": z((steps, B, n, 3), torch.float64),
+                    "vel": z((steps, B, n, 3), torch.float64),
+                    "u": z((steps, B, n, 3), torch.float64),
+                    "ca": z((steps, B, n), torch.uint8), "ctl": z((steps, B, n), torch.uint8),
+                    "P": z((steps, B, n), torch.int16), "state": z((steps, B), torch.int32),
+                    "vflags": z((steps, B, n), torch.int32)}
+        a = self._args(steps, hist)
+        F = self.table.struct()
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        L.check(L.lib().acl_fleet_trial_batch(ct.byref(F), ct.byref(a), ct.c_void_p(stream)),
+                "acl_fleet_trial_batch")
+        self.step += steps
+        return hist
+
+    def status(self):
+        """Per-trial supervisor state and counters, structured numpy [B]."""
+        arr = np.ascontiguousarray(self.ts.cpu().numpy())
+        return arr.view(L.TRIAL_STATUS_DTYPE).reshape(-1)
+
+    def fleet_status(self):
+        """{"fleet": the acl_fleet_episode_status_t records, "ticks": the last
+        step's acl_fleet_status_t records}, structured numpy arrays [B];
+        synchronises."""
+        def view(t, dt):
+            return np.ascontiguousarray(t.cpu().numpy()).view(dt).reshape(-1)
+        return {"fleet": view(self.fst, L.FLEET_EPISODE_STATUS_DTYPE),
+                "ticks": view(self._status, L.FLEET_STATUS_DTYPE)}
+
+    records = Trial.records
+
+
 def generate_formation_groups(seeds, n, fc, l, w, h, min_dist=2.0, max_candidates=0,
                               stream=None):
     """acl_generate_formation_groups: the reference's

@@ -1090,6 +1090,142 @@ acl_status_t acl_trial_init(const acl_trial_args_t* args, int32_t n, void* strea
 acl_status_t acl_trial_batch(const acl_formations_t* formations,
                              const acl_trial_args_t* args, void* stream);
 
+/* ---- trials on the message-level auction (added within ABI 11) ------------
+ * acl_fleet_trial_batch flies B trials of n <= 128 vehicles: the supervisor,
+ * the formation sequence and the controller starts of acl_trial_batch over
+ * the per-vehicle Auctioneers of acl_fleet_auction_batch, where an auction
+ * takes the time its messages take, a formation change interrupts the
+ * auction in flight and every vehicle adopts, and starts its controller, on
+ * its own. An added symbol: ACL_ABI_VERSION stays 11 (no existing struct or
+ * call changed). Per global step s = step0 + k, for every swarm not yet
+ * COMPLETE / TERMINATE, every launch stream-ordered, nothing synchronises:
+ *   1. commit: a formation requested by the last supervisor tick commits as
+ *      step 1 of acl_trial_batch does (fidx[b] changes, every controller
+ *      stops and sends one zero command, P becomes the identity, ctl_on is
+ *      cleared, next_auction = settle_steps), and every vehicle's auctioneer
+ *      runs Auctioneer::setFormation (auctioneer.cpp:42-62), also when it is
+ *      open ("Interrupting current auction"): reset() -- open = 0,
+ *      biditer = 0, the bid table cleared, the current and next buckets
+ *      cleared --, its row Pt[b][v] the identity, just_received = 1. The
+ *      START bucket, the receive queue, invalid, Rt, the start position,
+ *      final_* and done_tick stay, and a bid in flight stays in flight:
+ *      processBid never looks at the auction a bid belongs to, so bids of the
+ *      old formation's auction are filed or thrown away (n_thrown) in the new
+ *      formation's first auction;
+ *   2. auto-auction: the swarm's countdown is acl_trial_batch's (settle_steps
+ *      after a commit, then every auction_every steps). When it fires every
+ *      vehicle runs its own autoauctionCb (coordination_ros.cpp:322-359):
+ *      invalid[b][v] set -> ACL_FLEET_FLUSH, otherwise ACL_FLEET_START from
+ *      the current q, a restart when the vehicle is open; starts, restarts
+ *      and flushes are counted in fst as by acl_fleet_episode_batch. A commit
+ *      and an auto-auction in one step (settle_steps = 0) apply in that order;
+ *   3. ticks: ticks_per_step ticks of acl_fleet_auction_batch on the trial's
+ *      fleet state with the commands of (2), ACL_FLEET_NONE for the vehicles
+ *      of a swarm whose countdown did not fire. A finished trial is handed to
+ *      the fleet kernel with formation -1 and is left untouched (status[b]
+ *      then reads ACL_FLEET_BAD_INPUT, 0 ticks);
+ *   4. hand-off (newAssignmentCb, :284-303): a vehicle that raised
+ *      ACL_FLEET_V_ADOPTED during this step's ticks flies its new row from
+ *      this step's controller on and starts its controller (ctl_on[b][v] = 1,
+ *      first_assignment_). If it is vehicle 0 -- the supervisor subscribes to
+ *      vehicle 0's assignment topic only (supervisor.py:110-113) -- its
+ *      message reaches the supervisor: received = 1, and n_assign[b][formation]
+ *      is incremented while logging. All rows equal -> control mode 0,
+ *      otherwise mode 1 and ts.per_vehicle = 1; P[b][v] is v's point in its
+ *      own row (acl_fleet_episode_batch step 3);
+ *   5. control, trajectories, supervisor: steps 3 and 4 of acl_trial_batch,
+ *      with its arithmetic, its parameters (acl_trial_params_t), its status
+ *      (acl_trial_status_t) and its records (dist, t_conv, t_avoid, n_assign).
+ * Model limits: all vehicles of a swarm commit and fire their auto-auction
+ * timers on the same step; the 5 Hz spin delay is not modelled (a formation
+ * commits at the step after the tick that requested it); the limits of
+ * acl_fleet_auction_batch hold (latency below one tick, per-sender FIFO,
+ * queue_cap); n <= 128; tp.ep.auction_latency and tp.ep.assignment must be 0
+ * (the operator's Hungarian has no messages: acl_trial_batch keeps that
+ * mode); the other limits of acl_trial_batch. In acl_trial_status_t,
+ * n_auctions counts the auto-auction steps that issued commands; n_invalid,
+ * n_skipped and n_disagree stay 0: the vehicle events go to fst[b]
+ * (acl_fleet_episode_status_t), as for acl_fleet_episode_batch.
+ * Device pointers, updated in place (a trial continues across calls): the
+ * trial arrays of acl_trial_args_t (without flush); the fleet state and
+ * output arrays of acl_fleet_auction_args_t (vflags sticky; status is the
+ * last step's call); adopt_step [B][n] (the global step of the vehicle's last
+ * adoption, -1 if none); fst [B]; the optional histories of acl_trial_args_t
+ * and vflags_hist [steps][B][n] (the ACL_FLEET_V_* raised during step k).
+ * acl_fleet_trial_init sets the trial state as acl_trial_init does, the fleet
+ * state of freshly constructed auctioneers (identity rows, just_received = 0,
+ * who = -1, every other fleet array, fst and the workspace 0) and
+ * adopt_step = -1; q and vel are the caller's.
+ * workspace: acl_fleet_trial_workspace_bytes(n, B, queue_cap) bytes (the
+ * fleet workspace, the control hand-off region, the u / u_safe / ca scratch,
+ * the command buffer), handed back unchanged with the same n, B, queue_cap.
+ * The first step of a call builds the control hand-off from the rows alone.
+ * Per swarm, not argument errors: a trial with a formation index outside
+ * [0, n_formations) in fseq ends at once (TERMINATE, nothing of the table
+ * read, its fidx 0); a swarm that holds a row that is not a permutation at
+ * the start of a call is flagged ACL_FLEET_BAD_INPUT in fst and left
+ * untouched by the call: no commit, no ticks, no control, no supervisor tick,
+ * its state unchanged and its history rows not written (vflags_hist: 0). */
+typedef struct {
+  int32_t B;
+  int32_t K;
+  int32_t step0;
+  int32_t steps;
+  int32_t ticks_per_step; /* >= 1 */
+  int32_t max_iter;       /* as acl_fleet_auction_args_t */
+  int32_t queue_cap;
+  const int32_t* fseq;    /* [B][K] ... the arrays of acl_trial_args_t */
+  int32_t* fidx;
+  double* q;
+  double* vel;
+  uint16_t* P;
+  acl_trial_status_t* ts;
+  uint8_t* ctl_on;
+  double* ring_u;
+  uint8_t* ring_ca;
+  double* posf;
+  double* dist;
+  double* t_conv;
+  double* t_avoid;
+  int32_t* n_assign;
+  uint16_t* Pt;           /* [B][n][n] ... the arrays of acl_fleet_auction_args_t */
+  uint8_t* open;
+  uint8_t* invalid;
+  uint8_t* just_received;
+  int32_t* biditer;
+  float* price;
+  int32_t* who;
+  double* Rt;
+  float* final_price;
+  int32_t* final_who;
+  int32_t* done_tick;
+  int32_t* vflags;
+  int32_t* n_thrown;
+  int32_t* n_tally;
+  int32_t* queue_len;
+  acl_fleet_status_t* status;
+  int32_t* adopt_step;    /* [B][n] in/out */
+  acl_fleet_episode_status_t* fst; /* [B] in/out */
+  double* q_hist;         /* optional histories, as acl_trial_args_t */
+  double* vel_hist;
+  double* u_hist;
+  uint8_t* ca_hist;
+  uint8_t* ctl_hist;
+  uint16_t* P_hist;
+  int32_t* state_hist;
+  int32_t* vflags_hist;   /* [steps][B][n] or NULL */
+  void* workspace;
+  size_t workspace_bytes;
+  acl_cntrl_gains_t cntrl;
+  acl_safety_params_t safety;
+  acl_trial_params_t tp;
+} acl_fleet_trial_args_t;
+
+size_t acl_fleet_trial_workspace_bytes(int32_t n, int32_t B, int32_t queue_cap);
+acl_status_t acl_fleet_trial_init(const acl_fleet_trial_args_t* args, int32_t n, void* stream);
+acl_status_t acl_fleet_trial_batch(const acl_formations_t* formations,
+                                   const acl_fleet_trial_args_t* args, void* stream);
+
 /* ---- random formation groups on the device -----------
  * Replaces aclswarm_sim/nodes/generate_random_formation.py:59-80
  * generate_formation_group(n, fc, l, w, h, min_dist) after

@@ -38,6 +38,7 @@ EXPORTS = (
     "acl_control_batch", "acl_write_assignment_log", "acl_read_assignment_log",
     "acl_hungarian_batch", "acl_cbaa_step_batch", "acl_vehicle_start_batch",
     "acl_fleet_workspace_bytes", "acl_fleet_auction_batch",
+    "acl_fleet_delay_workspace_bytes", "acl_fleet_delay_auction_batch",
     "acl_fleet_episode_workspace_bytes", "acl_fleet_episode_batch",
     "acl_default_episode_params", "acl_episode_workspace_bytes", "acl_episode_batch",
     "acl_default_trial_params", "acl_trial_workspace_bytes", "acl_trial_init", "acl_trial_batch",
@@ -137,6 +138,13 @@ FLEET_QUIESCENT, FLEET_OVERFLOW, FLEET_BAD_INPUT = 0x1, 0x2, 0x4
 FLEET_V_STARTED, FLEET_V_BAD_ROW, FLEET_V_CONSENSUS = 0x01, 0x02, 0x04
 FLEET_V_ADOPTED, FLEET_V_INVALID, FLEET_V_OVERFLOW = 0x08, 0x10, 0x20
 FLEET_MAX_N = 128
+FLEET_MAX_LAT = 64
+
+
+class FleetDelayArgs(ct.Structure):
+    """acl_fleet_delay_args_t (added within ABI 11): the fleet auction with
+    per-link message latency, lat [B][n][n] u8 receiver-major, in ticks."""
+    _fields_ = [("base", FleetAuctionArgs), ("lat", ct.c_void_p), ("max_lat", ct.c_int32)]
 
 FLEET_STATUS_DTYPE = np.dtype([(k, "<i4") for k in ("ticks_run", "n_open", "n_queued", "flags")])
 
@@ -334,6 +342,11 @@ def lib():
     L.acl_fleet_auction_batch.argtypes = [ct.POINTER(Formations), ct.POINTER(FleetAuctionArgs),
                                           VP]
     L.acl_fleet_auction_batch.restype = ct.c_int
+    L.acl_fleet_delay_workspace_bytes.argtypes = [I32, I32, I32, I32]
+    L.acl_fleet_delay_workspace_bytes.restype = SZ
+    L.acl_fleet_delay_auction_batch.argtypes = [ct.POINTER(Formations),
+                                                ct.POINTER(FleetDelayArgs), VP]
+    L.acl_fleet_delay_auction_batch.restype = ct.c_int
     L.acl_fleet_episode_workspace_bytes.argtypes = [I32, I32, I32]
     L.acl_fleet_episode_workspace_bytes.restype = SZ
     L.acl_fleet_episode_batch.argtypes = [ct.POINTER(Formations), ct.POINTER(FleetEpisodeArgs),

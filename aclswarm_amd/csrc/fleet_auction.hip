@@ -31,6 +31,16 @@
 // copying them. A bid in flight is read from its sender's own table (which
 // does not change between publication and the next delivery); only a command
 // that resets a table with a bid still in flight copies it aside first.
+//
+// The delay instantiations (D; acl_fleet_delay_auction_batch) differ in
+// delivery only. Link (u -> w) takes lat[w][u] ticks, so a bid outlives its
+// sender's table: every publication is appended by copy to the sender's
+// publication log, a ring in the workspace (fleet_dev.h sizes it), and
+// delivery reads the log instead of the table: receiver w looks at the log
+// headers of each subscribed sender that has anything in flight, one header
+// per lane, and a ballot picks the entries that are due at w in this tick.
+// The latency matrix is validated and staged in LDS (n^2 bytes) before any
+// state is touched. The processing phase is the same code.
 #include "common.h"
 #include "cbaa_select_dev.h"  // step_select
 #include "fleet_dev.h"        // FleetMeta, fleet_layout, role_phys, the table helpers
@@ -77,7 +87,61 @@ struct FleetParams {
   int32_t* hist_biditer;
   uint8_t* hist_open;
   unsigned char* ws;
+  const uint8_t* lat;  // [B][n][n] receiver-major; the delay instantiations only
+  int max_lat;
 };
+
+// What the delay instantiations stage in LDS on top of the kernel's own: every
+// vehicle's log bookkeeping, the latency matrix lat[w * n + u] and each
+// sender's slowest link. (A function-scope variable, so that the
+// instantiations without delay allocate none of it.)
+template <int S>
+struct FleetDelayLds {
+  FleetLog log[kFleetMaxN];
+  int reach[kFleetMaxN];
+  unsigned char lat[64 * S * 64 * S];
+};
+
+template <int S>
+__device__ __forceinline__ FleetDelayLds<S>& fleet_delay_lds() {
+  __shared__ FleetDelayLds<S> d;
+  return d;
+}
+
+// A publication in the delay model: the table (p, w) with its iter and
+// publication tick goes into the next slot of the vehicle's log (hdr, tab:
+// the vehicle's R headers and tables). cnt, head, last_pub are wave-uniform
+// copies of the bookkeeping (FleetLog); the caller stores them.
+template <int S>
+__device__ __forceinline__ void fleet_log_append(int& cnt, int& head, int& last_pub, int* hdr,
+                                                 float* tab, int R, int n, int lane, int tick,
+                                                 int iter, const float (&p)[S],
+                                                 const int (&w)[S]) {
+  // Slot reuse. The ring has 2 max_lat slots and a vehicle publishes at most
+  // twice per publication tick (fleet_dev.h), so the entry this one overwrites
+  // was published at least max_lat ticks earlier: the delivery phase of every
+  // tick it was due in has run. And no delivery runs now: publications happen
+  // in the command and processing phases, which the workgroup barriers the
+  // tick loop already has separate from every delivery phase.
+  const int slot = head;
+  if (lane == 0) {
+    hdr[2 * slot] = tick;
+    hdr[2 * slot + 1] = iter;
+  }
+  float* dp = tab + (size_t)slot * 2 * n;
+  int32_t* dw = reinterpret_cast<int32_t*>(dp + n);
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const int j = lane + 64 * s;
+    if (j < n) {
+      dp[j] = p[s];
+      dw[j] = w[s];
+    }
+  }
+  head = slot + 1 >= R ? 0 : slot + 1;
+  cnt = cnt < R ? cnt + 1 : R;
+  last_pub = tick;
+}
 
 __device__ __forceinline__ bool mask_has(const unsigned long long (&m)[2], int u) {
   return (((u >> 6) ? m[1] : m[0]) >> (u & 63)) & 1ull;
@@ -123,7 +187,7 @@ __device__ __forceinline__ void fleet_sub_mask(const unsigned long long* adjrow,
   sub[1] = ((unsigned long long)w3 << 32) | w2;
 }
 
-template <int S>
+template <int S, bool D>
 __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
     fleet_auction_kernel(const FleetParams P) {
   constexpr int W = FleetWaves<S>::value;
@@ -155,7 +219,32 @@ __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
     }
     return;
   }
-  const FleetLayout L = fleet_layout(n, cap);
+  // ---- delay: the swarm's latency matrix, checked before any state is touched ----
+  FleetDelayLds<S>& dl = fleet_delay_lds<S>();  // (unused, so not allocated, without D)
+  const int R = D ? fleet_log_len(P.max_lat) : 0;  // a vehicle's log, in entries
+  if constexpr (D) {
+    const uint8_t* latb = P.lat + (size_t)b * n * n;
+    if (tid < n) dl.reach[tid] = 1;  // (n = 1: no link, a bid is in flight for one tick)
+    __syncthreads();
+    bool bad = false;
+    for (int k = tid; k < n * n; k += 64 * W) {
+      const int w = k / n, u = k - w * n;
+      int l = latb[k];
+      if (u == w) l = 1;  // ignored
+      else if (l < 1 || l > P.max_lat) bad = true;
+      else atomicMax(&dl.reach[u], l);
+      dl.lat[k] = (unsigned char)l;
+    }
+    if (__syncthreads_or(bad)) {  // block-uniform: the swarm is untouched
+      if (tid == 0) {
+        acl_fleet_status_t st;
+        st.ticks_run = 0; st.n_open = 0; st.n_queued = 0; st.flags = ACL_FLEET_BAD_INPUT;
+        P.status[b] = st;
+      }
+      return;
+    }
+  }
+  const FleetLayout L = fleet_layout(n, cap, R);
   unsigned char* ws = P.ws + (size_t)b * L.total;
   int* hdr = reinterpret_cast<int*>(ws);
   FleetMeta* meta_g = reinterpret_cast<FleetMeta*>(ws + L.meta);
@@ -165,6 +254,9 @@ __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
   float* bucket_g = reinterpret_cast<float*>(ws + L.bucket);
   int* queue_g = reinterpret_cast<int*>(ws + L.queue);
   const size_t ew = 2 + tw;  // a queue entry in words
+  FleetLog* log_g = reinterpret_cast<FleetLog*>(ws + L.log);
+  int* loghdr_g = reinterpret_cast<int*>(ws + L.loghdr);   // [n][R] (publication tick, iter)
+  float* logtab_g = reinterpret_cast<float*>(ws + L.logtab);  // [n][R] tables
   const size_t vb = (size_t)b * n;  // this swarm's first vehicle in the [B][n] arrays
   const int NW = (n + 63) >> 6;
   const unsigned long long* adjf = P.adj + (size_t)f * n * NW;
@@ -179,6 +271,13 @@ __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
     meta_s[tid] = meta_g[tid];
     open_s[tid] = P.open[vb + tid] != 0;
     biditer_s[tid] = P.biditer[vb + tid];
+    if constexpr (D) {
+      // (clamped: a workspace that was not zero-filled must not index past the log)
+      const int c = log_g[tid].cnt, h = log_g[tid].head;
+      dl.log[tid].cnt = c < 0 ? 0 : c > R ? R : c;
+      dl.log[tid].head = (unsigned)h < (unsigned)R ? h : 0;
+      dl.log[tid].last_pub = log_g[tid].last_pub;
+    }
   }
   if (tid == 0) {
     ovf_s = 0;
@@ -212,12 +311,16 @@ __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
       FleetMeta m = meta_s[v];
       float* pr = P.price + (vb + v) * n;
       int32_t* wh = P.who + (vb + v) * n;
-      if (m.live) {  // the bid in flight outlives the table it was read from
-        float* sp = stale_g + (size_t)v * tw;
-        fleet_copy_table<S>(sp, reinterpret_cast<int32_t*>(sp + n), pr, wh, n, lane);
-        m.stale = 1;
-        m.stale_iter = m.live_iter;
-        m.live = 0;
+      if constexpr (D) {  // unused: what is in flight is in the log
+        m.live = m.live_iter = m.stale = m.stale_iter = 0;
+      } else {
+        if (m.live) {  // the bid in flight outlives the table it was read from
+          float* sp = stale_g + (size_t)v * tw;
+          fleet_copy_table<S>(sp, reinterpret_cast<int32_t*>(sp + n), pr, wh, n, lane);
+          m.stale = 1;
+          m.stale_iter = m.live_iter;
+          m.live = 0;
+        }
       }
       // reset()
       int open = 0;
@@ -263,18 +366,33 @@ __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
         for (int s = 0; s < S; ++s) own_p[s] = 0.0f;
         unsigned best;
         const int task = step_select<S>(o, qx, qy, qz, pf, n, lane, own_p, best);
+        float bp[S];
+        int bw[S];
 #pragma unroll
         for (int s = 0; s < S; ++s) {
           const int j = lane + 64 * s;
+          const bool mine = j == task;
+          bp[s] = mine ? __uint_as_float(best) : 0.0f;
+          bw[s] = mine ? v : -1;
           if (j < n) {
-            const bool mine = j == task;
-            pr[j] = mine ? __uint_as_float(best) : 0.0f;
-            wh[j] = mine ? v : -1;
+            pr[j] = bp[s];
+            wh[j] = bw[s];
           }
         }
         open = 1;
-        m.live = 1;
-        m.live_iter = 0;
+        if constexpr (D) {  // a command's bid: the tick before the call's first
+          int lc = dl.log[v].cnt, lh = dl.log[v].head, lp = dl.log[v].last_pub;
+          fleet_log_append<S>(lc, lh, lp, loghdr_g + (size_t)v * R * 2,
+                              logtab_g + (size_t)v * R * tw, R, n, lane, tick0 - 1, 0, bp, bw);
+          if (lane == 0) {
+            dl.log[v].cnt = lc;
+            dl.log[v].head = lh;
+            dl.log[v].last_pub = lp;
+          }
+        } else {
+          m.live = 1;
+          m.live_iter = 0;
+        }
         vf = ACL_FLEET_V_STARTED;
         __builtin_amdgcn_wave_barrier();  // st is reused by the next vehicle
       }
@@ -296,7 +414,11 @@ __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
   __syncthreads();  // what the commands wrote is visible
   bool busy = false;
   if (tid < n) {
-    const bool flying = meta_s[tid].live || meta_s[tid].stale;
+    bool flying;
+    if constexpr (D)  // until the delivery phase of its slowest link's tick has run
+      flying = dl.log[tid].cnt > 0 && dl.log[tid].last_pub + dl.reach[tid] >= tick0;
+    else
+      flying = meta_s[tid].live || meta_s[tid].stale;
     busy = flying || (open_s[tid] && meta_s[tid].qlen > 0);
     if (flying) atomicOr(&pend_s[1][tid >> 6], 1ull << (tid & 63));
   }
@@ -321,6 +443,50 @@ __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
         while (mm) {
           const int u = hw * 64 + __builtin_ctzll(mm);
           mm &= mm - 1;
+          if constexpr (D) {
+            // the sender's log, oldest entry first, lane k its k-th header: the
+            // entries due on this link now are appended in publication order
+            const int cnt = __builtin_amdgcn_readfirstlane(dl.log[u].cnt);
+            const int first = __builtin_amdgcn_readfirstlane(dl.log[u].head) - cnt;  // mod R
+            const int due = tick0 + t - __builtin_amdgcn_readfirstlane((int)dl.lat[w * n + u]);
+            const int* uh = loghdr_g + (size_t)u * R * 2;
+            const float* ut = logtab_g + (size_t)u * R * tw;
+            for (int base = 0; base < cnt; base += 64) {
+              const int k = base + lane;
+              int hs = first + k;
+              if (hs < 0) hs += R;
+              int hp = 0, hi = 0;
+              if (k < cnt) {
+                hp = uh[2 * hs];
+                hi = uh[2 * hs + 1];
+              }
+              unsigned long long dm = __ballot(k < cnt && hp == due);
+              while (dm) {
+                const int kk = __builtin_ctzll(dm);
+                dm &= dm - 1;
+                if (ql == cap) {
+                  dropped = true;
+                  continue;
+                }
+                int es = first + base + kk;
+                if (es < 0) es += R;
+                int slot = qh + ql;
+                if (slot >= cap) slot -= cap;
+                int* e = qw + (size_t)slot * ew;
+                const int it = __builtin_amdgcn_readlane(hi, kk);
+                if (lane == 0) {
+                  e[0] = u;
+                  e[1] = it;
+                }
+                const float* sp = ut + (size_t)es * tw;
+                float* dp = reinterpret_cast<float*>(e + 2);
+                fleet_copy_table<S>(dp, reinterpret_cast<int32_t*>(dp + n), sp,
+                                    reinterpret_cast<const int32_t*>(sp + n), n, lane);
+                ++ql;
+              }
+            }
+            continue;
+          }
           for (int k = 0; k < 2; ++k) {  // the older bid first
             const bool have = k == 0 ? meta_s[u].stale != 0 : meta_s[u].live != 0;
             if (!have) continue;
@@ -372,6 +538,13 @@ __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
       FleetMeta m = meta_s[v];
       m.live = 0;  // delivered above
       m.stale = 0;
+      int lc = 0, lh = 0, lp = 0;  // the vehicle's log bookkeeping (D)
+      if constexpr (D) {
+        m.live_iter = m.stale_iter = 0;  // unused: what is in flight is in the log
+        lc = dl.log[v].cnt;
+        lh = dl.log[v].head;
+        lp = dl.log[v].last_pub;
+      }
       int open = open_s[v];
       int bi = biditer_s[v];
       if (open && m.qlen > 0) {
@@ -546,6 +719,9 @@ __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
               mp[s] = 0.0f;
               mw[s] = -1;
             }
+          } else if constexpr (D) {  // notifySendBid, publication tick: this one
+            fleet_log_append<S>(lc, lh, lp, loghdr_g + (size_t)v * R * 2,
+                                logtab_g + (size_t)v * R * tw, R, n, lane, tick0 + t, bi, mp, mw);
           } else {
             m.live = 1;  // notifySendBid
             m.live_iter = bi;
@@ -568,8 +744,17 @@ __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
         meta_s[v] = m;
         open_s[v] = open;
         biditer_s[v] = bi;
-        if (m.live || (open && m.qlen > 0)) busy_s[t & 1] = 1;
-        if (m.live) atomicOr(&pend_s[t & 1][v >> 6], 1ull << (v & 63));
+        bool flying;
+        if constexpr (D) {  // past the next tick's delivery?
+          dl.log[v].cnt = lc;
+          dl.log[v].head = lh;
+          dl.log[v].last_pub = lp;
+          flying = lc > 0 && lp + dl.reach[v] >= tick0 + t + 1;
+        } else {
+          flying = m.live != 0;
+        }
+        if (flying || (open && m.qlen > 0)) busy_s[t & 1] = 1;
+        if (flying) atomicOr(&pend_s[t & 1][v >> 6], 1ull << (v & 63));
       }
     }
     ++t;
@@ -585,6 +770,11 @@ __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
   // ---- the state back; history rows past the last tick run; the status ----
   if (tid < n) {
     meta_g[tid] = meta_s[tid];
+    if constexpr (D) {
+      log_g[tid].cnt = dl.log[tid].cnt;
+      log_g[tid].head = dl.log[tid].head;
+      log_g[tid].last_pub = dl.log[tid].last_pub;
+    }
     P.open[vb + tid] = (uint8_t)open_s[tid];
     P.biditer[vb + tid] = biditer_s[tid];
     P.queue_len[vb + tid] = meta_s[tid].qlen;
@@ -615,33 +805,50 @@ extern "C" size_t acl_fleet_workspace_bytes(int32_t n, int32_t B, int32_t queue_
   return (size_t)B * acl_amd::fleet_layout(n, queue_cap).total;
 }
 
-extern "C" acl_status_t acl_fleet_auction_batch(const acl_formations_t* F,
-                                                const acl_fleet_auction_args_t* a, void* stream) {
+extern "C" size_t acl_fleet_delay_workspace_bytes(int32_t n, int32_t B, int32_t queue_cap,
+                                                  int32_t max_lat) {
   using namespace acl_amd;
-  if (!F || !a) return acl__set_error("acl_fleet_auction_batch: null argument");
+  if (n < 1 || n > kFleetMaxN || B < 1 || queue_cap < 1 || max_lat < 1 || max_lat > kFleetMaxLat)
+    return 0;
+  return (size_t)B * fleet_layout(n, queue_cap, fleet_log_len(max_lat)).total;
+}
+
+namespace acl_amd {
+
+static acl_status_t fleet_error(const char* entry, const char* what) {
+  char msg[192];
+  snprintf(msg, sizeof msg, "%s: %s", entry, what);
+  return acl__set_error(msg);
+}
+
+// The argument checks the two entries share; *launch says whether anything
+// is left to do (B > 0). The workspace size is the entry's own check.
+static acl_status_t fleet_check(const char* entry, const acl_formations_t* F,
+                                const acl_fleet_auction_args_t* a, bool* launch) {
+  *launch = false;
+  if (!F || !a) return fleet_error(entry, "null argument");
   const int n = F->n;
-  if (n < 1 || n > kFleetMaxN)
-    return acl__set_error("acl_fleet_auction_batch: n out of range [1, 128]");
+  if (n < 1 || n > kFleetMaxN) return fleet_error(entry, "n out of range [1, 128]");
   if (a->B < 0 || a->ticks < 0 || a->max_iter < 0)
-    return acl__set_error("acl_fleet_auction_batch: B < 0, ticks < 0 or max_iter < 0");
-  if (a->queue_cap < 1) return acl__set_error("acl_fleet_auction_batch: queue_cap < 1");
+    return fleet_error(entry, "B < 0, ticks < 0 or max_iter < 0");
+  if (a->queue_cap < 1) return fleet_error(entry, "queue_cap < 1");
   if (a->B == 0) return ACL_OK;
-  if (F->n_formations < 1)
-    return acl__set_error("acl_fleet_auction_batch: the formation table is empty");
+  if (F->n_formations < 1) return fleet_error(entry, "the formation table is empty");
   if (!F->p || !F->adj || !a->fidx || !a->Pt || !a->open || !a->invalid || !a->just_received ||
       !a->biditer || !a->price || !a->who || !a->Rt || !a->final_price || !a->final_who ||
       !a->done_tick || !a->vflags || !a->n_thrown || !a->n_tally || !a->queue_len || !a->status ||
       !a->workspace)
-    return acl__set_error("acl_fleet_auction_batch: required pointer is NULL");
-  if (a->cmd && !a->q)
-    return acl__set_error("acl_fleet_auction_batch: cmd is given and q is NULL");
+    return fleet_error(entry, "required pointer is NULL");
+  if (a->cmd && !a->q) return fleet_error(entry, "cmd is given and q is NULL");
   if (a->cmd && a->ticks < 1)
-    return acl__set_error("acl_fleet_auction_batch: a call with cmd must run at least one tick");
-  if (a->workspace_bytes < acl_fleet_workspace_bytes(n, a->B, a->queue_cap))
-    return acl__set_error("acl_fleet_auction_batch: workspace_bytes is too small "
-                          "(acl_fleet_workspace_bytes)");
+    return fleet_error(entry, "a call with cmd must run at least one tick");
+  *launch = true;
+  return ACL_OK;
+}
+
+static FleetParams fleet_params(const acl_formations_t* F, const acl_fleet_auction_args_t* a) {
   FleetParams P;
-  P.n = n; P.B = a->B; P.F = F->n_formations; P.ticks = a->ticks; P.max_iter = a->max_iter;
+  P.n = F->n; P.B = a->B; P.F = F->n_formations; P.ticks = a->ticks; P.max_iter = a->max_iter;
   P.cap = a->queue_cap; P.p = F->p;
   P.adj = reinterpret_cast<const unsigned long long*>(F->adj);
   P.fidx = a->fidx; P.q = a->q; P.cmd = a->cmd; P.Pt = a->Pt; P.open = a->open;
@@ -651,12 +858,57 @@ extern "C" acl_status_t acl_fleet_auction_batch(const acl_formations_t* F,
   P.n_thrown = a->n_thrown; P.n_tally = a->n_tally; P.queue_len = a->queue_len;
   P.status = a->status; P.hist_biditer = a->hist_biditer; P.hist_open = a->hist_open;
   P.ws = static_cast<unsigned char*>(a->workspace);
+  P.lat = nullptr;
+  P.max_lat = 0;
+  return P;
+}
+
+template <bool D>
+static acl_status_t fleet_launch(const FleetParams& P, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (n <= 64)
-    hipLaunchKernelGGL(fleet_auction_kernel<1>, dim3(a->B), dim3(64 * FleetWaves<1>::value), 0, s, P);
+  if (P.n <= 64)
+    hipLaunchKernelGGL((fleet_auction_kernel<1, D>), dim3(P.B), dim3(64 * FleetWaves<1>::value), 0,
+                       s, P);
   else
-    hipLaunchKernelGGL(fleet_auction_kernel<2>, dim3(a->B), dim3(64 * FleetWaves<2>::value), 0, s, P);
+    hipLaunchKernelGGL((fleet_auction_kernel<2, D>), dim3(P.B), dim3(64 * FleetWaves<2>::value), 0,
+                       s, P);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return acl__set_error(hipGetErrorString(e));
   return ACL_OK;
+}
+
+}  // namespace acl_amd
+
+extern "C" acl_status_t acl_fleet_auction_batch(const acl_formations_t* F,
+                                                const acl_fleet_auction_args_t* a, void* stream) {
+  using namespace acl_amd;
+  static const char entry[] = "acl_fleet_auction_batch";
+  bool launch;
+  const acl_status_t st = fleet_check(entry, F, a, &launch);
+  if (st != ACL_OK || !launch) return st;
+  if (a->workspace_bytes < acl_fleet_workspace_bytes(F->n, a->B, a->queue_cap))
+    return fleet_error(entry, "workspace_bytes is too small (acl_fleet_workspace_bytes)");
+  return fleet_launch<false>(fleet_params(F, a), stream);
+}
+
+extern "C" acl_status_t acl_fleet_delay_auction_batch(const acl_formations_t* F,
+                                                      const acl_fleet_delay_args_t* d,
+                                                      void* stream) {
+  using namespace acl_amd;
+  static const char entry[] = "acl_fleet_delay_auction_batch";
+  if (!d) return fleet_error(entry, "null argument");
+  const acl_fleet_auction_args_t* a = &d->base;
+  bool launch;
+  const acl_status_t st = fleet_check(entry, F, a, &launch);
+  if (st != ACL_OK) return st;
+  if (d->max_lat < 1 || d->max_lat > kFleetMaxLat)
+    return fleet_error(entry, "max_lat out of range [1, 64]");
+  if (!launch) return ACL_OK;
+  if (!d->lat) return fleet_error(entry, "lat is NULL");
+  if (a->workspace_bytes < acl_fleet_delay_workspace_bytes(F->n, a->B, a->queue_cap, d->max_lat))
+    return fleet_error(entry, "workspace_bytes is too small (acl_fleet_delay_workspace_bytes)");
+  FleetParams P = fleet_params(F, a);
+  P.lat = d->lat;
+  P.max_lat = d->max_lat;
+  return fleet_launch<true>(P, stream);
 }

@@ -25,21 +25,47 @@ static_assert(sizeof(FleetMeta) == 80, "FleetMeta layout");
 
 enum { kRoleZero = 0, kRoleCurr = 1, kRoleNext = 2 };
 
+// The delay entry's largest link latency, in ticks, and the length of a
+// vehicle's publication log for a given max_lat. A sender publishes at most
+// two bids per publication tick (one tally that goes on, and one START: a call
+// with a command runs at least one tick, so a second START has a later
+// publication tick), and a bid is due for the last time max_lat ticks after its
+// publication tick. The bids that are still due somewhere were therefore
+// published in the last max_lat publication ticks: at most 2 max_lat of them,
+// and a ring of that length never overwrites a bid that is still in flight.
+constexpr int kFleetMaxLat = 64;
+__host__ __device__ constexpr int fleet_log_len(int max_lat) { return 2 * max_lat; }
+
+// the delay entry's per-vehicle log bookkeeping (all zero: nothing published)
+struct FleetLog {
+  int cnt;       // valid entries, <= the ring's length
+  int head;      // the slot the next publication takes
+  int last_pub;  // publication tick of the newest entry
+  int pad;
+};
+static_assert(sizeof(FleetLog) == 16, "FleetLog layout");
+
 struct FleetLayout {
   size_t meta, qv, stale, bucket, queue, total;
+  size_t log, loghdr, logtab;  // the delay layout only
 };
 
 // per-swarm workspace: [tick i32, pad][meta n][start position n x 3 f64]
 // [stale table n][buckets n x 3 x n tables][queues n x cap entries]
-__host__ __device__ inline FleetLayout fleet_layout(int n, int cap) {
+// The delay layout (R = the log's length > 0) has no stale table and appends
+// [log bookkeeping n][log headers n x R x (tick, iter)][log tables n x R].
+__host__ __device__ inline FleetLayout fleet_layout(int n, int cap, int R = 0) {
   const size_t N = (size_t)n, tb = 8 * N;  // a table: price f32[n], who i32[n]
   FleetLayout L;
   L.meta = 16;
   L.qv = L.meta + N * sizeof(FleetMeta);
   L.stale = L.qv + N * 24;
-  L.bucket = L.stale + N * tb;
+  L.bucket = L.stale + (R ? 0 : N * tb);
   L.queue = L.bucket + N * 3 * N * tb;
-  L.total = L.queue + N * (size_t)cap * (8 + tb);
+  L.log = L.queue + N * (size_t)cap * (8 + tb);
+  L.loghdr = L.log + (R ? N * sizeof(FleetLog) : 0);
+  L.logtab = L.loghdr + N * (size_t)R * 8;
+  L.total = L.logtab + N * (size_t)R * tb;
   return L;
 }
 

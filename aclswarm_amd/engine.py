@@ -460,10 +460,20 @@ class FleetAuction:
     (Pt, open, invalid, just_received, biditer, price, who, Rt), the outputs
     (final_price, final_who, done_tick, vflags, n_thrown, n_tally, queue_len)
     and the workspace. just_received starts at 1 (a formation just set); the
-    caller may rewrite any state tensor between runs. Raises ValueError on a
-    malformed argument before anything runs."""
+    caller may rewrite any state tensor between runs.
 
-    def __init__(self, table, fidx, Pt=None, queue_cap=None, max_iter=0):
+    latency None: that entry exactly. Otherwise the fleet runs
+    acl_fleet_delay_auction_batch, where link (u -> w) of swarm b takes
+    latency[b][w][u] ticks: an int gives every link that latency, a contiguous
+    uint8 tensor [B][n][n] (receiver-major, on the table's device; the
+    diagonal is ignored) per-link values in 1..max_latency. max_latency
+    (<= 64) sizes the publication logs and defaults to the largest entry
+    (reading it synchronises once, in the constructor). The latencies are
+    fixed for the object's life. Raises ValueError on a malformed argument
+    before anything runs."""
+
+    def __init__(self, table, fidx, Pt=None, queue_cap=None, max_iter=0, latency=None,
+                 max_latency=None):
         n = table.n
         if n < 1 or n > L.FLEET_MAX_N:
             raise ValueError(f"FleetAuction: n = {n} out of range [1, {L.FLEET_MAX_N}]")
@@ -485,6 +495,7 @@ class FleetAuction:
             raise ValueError(f"FleetAuction: max_iter = {max_iter} < 0")
         self.table, self.fidx, self.n, self.B, self.device = table, fidx, n, B, dev
         self.queue_cap, self.max_iter = int(queue_cap), int(max_iter)
+        self.latency, self.max_latency = self._latency(latency, max_latency, B, n, dev)
         if Pt is None:
             Pt = torch.arange(n, dtype=torch.int16, device=dev).repeat(B, n, 1)
         self.Pt = Pt.clone().contiguous()
@@ -516,7 +527,36 @@ class FleetAuction:
                 raise ValueError(f"{what}: {name} must be a contiguous {dts[0]} tensor of shape "
                                  f"{shape} on {dev}")
 
+    @classmethod
+    def _latency(cls, latency, max_latency, B, n, dev):
+        """(lat [B][n][n] u8 tensor, max_lat), or (None, None) without latency."""
+        top = L.FLEET_MAX_LAT
+        if latency is None:
+            if max_latency is not None:
+                raise ValueError("FleetAuction: max_latency is given without latency")
+            return None, None
+        if isinstance(latency, (int, np.integer)) and not isinstance(latency, bool):
+            if not 1 <= int(latency) <= top:
+                raise ValueError(f"FleetAuction: latency = {latency} out of range [1, {top}]")
+            largest = int(latency)
+            latency = torch.full((B, n, n), largest, dtype=torch.uint8, device=dev)
+        else:
+            cls._check("FleetAuction", {"latency": (latency, (torch.uint8,), (B, n, n))}, dev)
+            largest = int(latency.max())
+            latency = latency.clone()
+        if max_latency is None:
+            max_latency = max(largest, 1)
+        if isinstance(max_latency, bool) or not isinstance(max_latency, (int, np.integer)):
+            raise ValueError("FleetAuction: max_latency must be an int")
+        if max_latency < largest or max_latency > top:
+            raise ValueError(f"FleetAuction: max_latency = {max_latency} must be at least the "
+                             f"largest latency ({largest}) and at most {top}")
+        return latency, int(max_latency)
+
     def workspace_bytes(self):
+        if self.latency is not None:
+            return int(L.lib().acl_fleet_delay_workspace_bytes(self.n, self.B, self.queue_cap,
+                                                               self.max_latency))
         return int(L.lib().acl_fleet_workspace_bytes(self.n, self.B, self.queue_cap))
 
     def run(self, ticks, q=None, cmd=None, history=False, stream=None):
@@ -547,7 +587,8 @@ class FleetAuction:
         if history:
             hist = {"biditer": torch.empty((ticks, B, n), dtype=torch.int32, device=dev),
                     "open": torch.empty((ticks, B, n), dtype=torch.uint8, device=dev)}
-        a = L.FleetAuctionArgs()
+        d = L.FleetDelayArgs()
+        a = d.base if self.latency is not None else L.FleetAuctionArgs()
         a.B, a.ticks, a.max_iter, a.queue_cap = B, ticks, self.max_iter, self.queue_cap
         a.fidx = self.fidx.data_ptr()
         a.q = q.data_ptr() if q is not None else None
@@ -565,8 +606,14 @@ class FleetAuction:
         F = self.table.struct()
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
-        L.check(L.lib().acl_fleet_auction_batch(ct.byref(F), ct.byref(a), ct.c_void_p(stream)),
-                "acl_fleet_auction_batch")
+        if self.latency is not None:
+            d.lat, d.max_lat = self.latency.data_ptr(), self.max_latency
+            L.check(L.lib().acl_fleet_delay_auction_batch(ct.byref(F), ct.byref(d),
+                                                          ct.c_void_p(stream)),
+                    "acl_fleet_delay_auction_batch")
+        else:
+            L.check(L.lib().acl_fleet_auction_batch(ct.byref(F), ct.byref(a), ct.c_void_p(stream)),
+                    "acl_fleet_auction_batch")
         return hist
 
     def status(self):

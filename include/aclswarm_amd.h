@@ -669,6 +669,77 @@ size_t acl_fleet_workspace_bytes(int32_t n, int32_t B, int32_t queue_cap);
 acl_status_t acl_fleet_auction_batch(const acl_formations_t* formations,
                                      const acl_fleet_auction_args_t* args, void* stream);
 
+/* ---- the fleet auction with per-link message latency (added within ABI 11) --
+ * acl_fleet_auction_batch with delivery replaced: everything above holds
+ * (commands, subscriptions, queues, buckets, processBid, consensus, adoption,
+ * quiescence, the call rules, queue overflow) except when a published bid
+ * reaches a queue. Added symbols: ACL_ABI_VERSION stays 11.
+ *
+ * Latency matrix. Per swarm, lat[b][w][u] (u8, receiver-major) is the number
+ * of ticks from sender u's publication to receiver w's queue. Entries with
+ * u != w must lie in 1..max_lat; the diagonal is ignored. max_lat is a call
+ * argument in 1..64. Link latencies are fixed for the life of a workspace:
+ * like n, B and queue_cap, the caller hands the same lat and max_lat back
+ * with every call, so each link stays FIFO.
+ *
+ * Publication ticks. Absolute ticks are the workspace's tick counter (the
+ * one done_tick reports). A bid published by the processing phase of tick T
+ * has publication tick T. A bid published by a START command of a call whose
+ * first tick is T0 has publication tick T0 - 1. A bid of sender u with
+ * publication tick P is appended to w's queue in the delivery phase of tick
+ * P + lat[b][w][u] -- if w subscribes to u under w's own row at that moment,
+ * exactly as above -- and is dropped with the overflow flags if the queue
+ * holds queue_cap bids.
+ *
+ * Order within one delivery phase, for one receiver: ascending sender id,
+ * then a sender's own bids in publication order; the processing-phase bid of
+ * a tick comes before a command's bid with the same publication tick.
+ *
+ * In flight. A bid of sender u is in flight until the delivery phase of tick
+ * P + reach[u] has run, reach[u] = max over w != u of lat[b][w][u] (1 when
+ * n = 1). A swarm is quiescent when nothing is in flight and no open vehicle
+ * has a queued bid. With every link at 1 tick this is acl_fleet_auction_batch
+ * tick for tick: the same state, outputs and statuses after every call.
+ * ticks = a then b equals a + b also with bids in flight across the boundary;
+ * a call with cmd != NULL must run at least one tick; bids in flight stay in
+ * flight through a command.
+ *
+ * Bad latency. A swarm whose lat holds an entry outside 1..max_lat off the
+ * diagonal gets ACL_FLEET_BAD_INPUT and is left untouched, exactly like an
+ * out-of-range fidx; the other swarms of the call run.
+ *
+ * Capacity. Every publication is kept by copy in its sender's publication
+ * log, a ring of 2 max_lat bids in the workspace. A sender publishes at most
+ * two bids per publication tick (one tally that goes on, and one START: a
+ * call with a command runs at least one tick, so a second START has a later
+ * publication tick), and a bid is due for the last time max_lat ticks after
+ * its publication tick, so the log never overwrites a bid in flight.
+ *
+ * Workspace: acl_fleet_delay_workspace_bytes(n, B, queue_cap, max_lat) bytes,
+ * zero-filled once and handed back unchanged with the same n, B, queue_cap,
+ * lat and max_lat. It is a layout of its own (the tick counter, per-vehicle
+ * bookkeeping, start positions, buckets and queues of the layout above, plus
+ * the publication logs: per vehicle 16 + 2 max_lat (8 + 8 n) bytes) and is not
+ * interchangeable with a workspace of acl_fleet_workspace_bytes: a swarm
+ * stays with the entry it started with. The argument checks are those of
+ * acl_fleet_auction_batch on `base`, plus: lat NULL, max_lat outside 1..64,
+ * workspace_bytes too small. n in [1, 128]. Stream-ordered, never
+ * synchronises.
+ *
+ * Not modelled: latencies that change over time, message loss, and latency in
+ * acl_fleet_episode_batch / acl_fleet_trial_batch (which run the entry
+ * above). */
+typedef struct {
+  acl_fleet_auction_args_t base; /* workspace: acl_fleet_delay_workspace_bytes */
+  const uint8_t* lat;            /* [B][n][n] receiver-major: lat[b][w][u], ticks from u to w */
+  int32_t max_lat;               /* 1..64: the largest entry lat may hold */
+} acl_fleet_delay_args_t;
+
+size_t acl_fleet_delay_workspace_bytes(int32_t n, int32_t B, int32_t queue_cap,
+                                       int32_t max_lat);
+acl_status_t acl_fleet_delay_auction_batch(const acl_formations_t* formations,
+                                           const acl_fleet_delay_args_t* args, void* stream);
+
 /* ---- closed-loop batched episodes ---------------------
  * B swarms flown for `steps` control periods in lockstep: the discrete-time
  * model of one vehicle's node graph (CoordinationROS + Safety) with a

@@ -15,10 +15,16 @@ per-vehicle CBAA protocol to its end:
           gathered with torch.index_select on the device from index lists
           built once, which is faster than a gather through host memory.
 
-Both are timed wall-clock between synchronisations after a warm-up, the two
-paths alternated in one session, and the medians reported; the paced loop's
-final tables must equal the fleet's. Writes one JSON document (--out) with
-both times, the fleet kernel's time per tick and the workspace bytes.
+With --latency L[,L...] a third path per L is alternated with them:
+
+  delay   one acl_fleet_delay_auction_batch call with every link at L ticks
+          (engine.FleetAuction(latency=L)): the same auction through the
+          publication logs; its final tables must equal the fleet's.
+
+All are timed wall-clock between synchronisations after a warm-up, the paths
+alternated in one session, and the medians reported; the paced loop's final
+tables must equal the fleet's. Writes one JSON document (--out) with the
+times, the fleet kernel's time per tick and the workspace bytes.
 """
 import argparse
 import json
@@ -101,7 +107,7 @@ def timed(fn, dev):
     return time.perf_counter() - t0, r
 
 
-def bench(n, B, F, reps, warmup, dev):
+def bench(n, B, F, reps, warmup, dev, latencies=()):
     T, adj, fidx, q = make_case(n, B, F, 1000 + n, dev)
     d_max = int(adj.sum(axis=2).max())
     ticks = 2 * n * d_max + 8
@@ -116,9 +122,20 @@ def bench(n, B, F, reps, warmup, dev):
         dt, _ = timed(lambda: f.run(ticks, q=q, cmd=cmd), dev)
         return dt, f
 
-    t_fleet, t_paced = [], []
+    def delay(lat):
+        # (a bid crosses a link in lat ticks instead of 1: lat times the ticks are enough)
+        d = engine.FleetAuction(T, fidx, latency=lat)
+        d.ws = torch.zeros(d.workspace_bytes(), dtype=torch.uint8, device=dev)
+        dt, _ = timed(lambda: d.run(ticks * lat, q=q, cmd=cmd), dev)
+        return dt, d
+
+    t_fleet, t_paced, t_delay, last = [], [], {lat: [] for lat in latencies}, {}
     for r in range(warmup + reps):
         dt_f, f = fleet()
+        for lat in latencies:
+            dt_d, last[lat] = delay(lat)
+            if r >= warmup:
+                t_delay[lat].append(dt_d)
         dt_p, who_p = timed(paced.run, dev)
         if r >= warmup:
             t_fleet.append(dt_f)
@@ -129,7 +146,19 @@ def bench(n, B, F, reps, warmup, dev):
     assert same, "the paced loop and the fleet call disagree"
     mf, mp = statistics.median(t_fleet), statistics.median(t_paced)
     tr = int(st["ticks_run"].max())
-    return dict(n=n, B=B, formations=F, d_max=d_max, queue_cap=fa.queue_cap,
+    delays = []
+    for lat in latencies:
+        d, sd = last[lat], last[lat].status()
+        assert (sd["flags"] == L.FLEET_QUIESCENT).all() and (sd["n_open"] == 0).all()
+        assert bool((d.final_who == f.final_who).all()), "the delay entry's tables differ"
+        md, trd = statistics.median(t_delay[lat]), int(sd["ticks_run"].max())
+        delays.append(dict(latency=lat, delay_ms=md * 1e3,
+                           delay_ms_all=[x * 1e3 for x in t_delay[lat]],
+                           ticks_run_max=trd, ticks_run_min=int(sd["ticks_run"].min()),
+                           delay_us_per_tick=md * 1e6 / trd, delay_over_fleet=md / mf,
+                           workspace_bytes=d.workspace_bytes(), tables_equal=True,
+                           thrown=int(d.n_thrown.sum().item())))
+    return dict(delay=delays, n=n, B=B, formations=F, d_max=d_max, queue_cap=fa.queue_cap,
                 ticks_run_max=tr, ticks_run_min=int(st["ticks_run"].min()),
                 fleet_ms=mf * 1e3, fleet_ms_all=[x * 1e3 for x in t_fleet],
                 fleet_us_per_tick=mf * 1e6 / tr,
@@ -147,6 +176,8 @@ def main():
     ap.add_argument("--formations", type=int, default=8)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--latency", default="", help="uniform link latencies in ticks, "
+                    "comma-separated: also time acl_fleet_delay_auction_batch at each")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fleet_auction",
                                                   "latency.json"))
     a = ap.parse_args()
@@ -154,7 +185,8 @@ def main():
     res = []
     for s in a.shapes.split(","):
         n, B = (int(x) for x in s.split("x"))
-        r = bench(n, B, a.formations, a.reps, a.warmup, dev)
+        r = bench(n, B, a.formations, a.reps, a.warmup, dev,
+                  [int(x) for x in a.latency.split(",") if x])
         print(json.dumps(r), flush=True)
         res.append(r)
     doc = dict(device=torch.cuda.get_device_name(dev), reps=a.reps, warmup=a.warmup,

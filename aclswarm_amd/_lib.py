@@ -40,6 +40,9 @@ EXPORTS = (
     "acl_fleet_workspace_bytes", "acl_fleet_auction_batch",
     "acl_fleet_delay_workspace_bytes", "acl_fleet_delay_auction_batch",
     "acl_fleet_episode_workspace_bytes", "acl_fleet_episode_batch",
+    "acl_fleet_delay_episode_workspace_bytes", "acl_fleet_delay_episode_batch",
+    "acl_fleet_delay_trial_workspace_bytes", "acl_fleet_delay_trial_init",
+    "acl_fleet_delay_trial_batch",
     "acl_default_episode_params", "acl_episode_workspace_bytes", "acl_episode_batch",
     "acl_default_trial_params", "acl_trial_workspace_bytes", "acl_trial_init", "acl_trial_batch",
     "acl_fleet_trial_workspace_bytes", "acl_fleet_trial_init", "acl_fleet_trial_batch",
@@ -198,6 +201,12 @@ class FleetEpisodeArgs(ct.Structure):
         ("ep", EpisodeParams)]
 
 
+class FleetDelayEpisodeArgs(ct.Structure):
+    """acl_fleet_delay_episode_args_t (added within ABI 11): the episodes with
+    per-link message latency."""
+    _fields_ = [("base", FleetEpisodeArgs), ("lat", ct.c_void_p), ("max_lat", ct.c_int32)]
+
+
 FLEET_EPISODE_STATUS_DTYPE = np.dtype([(k, "<i4") for k in (
     "flags", "ticks_run", "n_started", "n_restarted", "n_flushed", "n_consensus", "n_adopted",
     "n_invalid")])
@@ -249,6 +258,12 @@ class FleetTrialArgs(ct.Structure):
             "ca_hist", "ctl_hist", "P_hist", "state_hist", "vflags_hist", "workspace")] + [
         ("workspace_bytes", ct.c_size_t), ("cntrl", CntrlGains), ("safety", SafetyParams),
         ("tp", TrialParams)]
+
+
+class FleetDelayTrialArgs(ct.Structure):
+    """acl_fleet_delay_trial_args_t (added within ABI 11): the trials with
+    per-link message latency."""
+    _fields_ = [("base", FleetTrialArgs), ("lat", ct.c_void_p), ("max_lat", ct.c_int32)]
 
 
 HUNG_BAD_INPUT = 0x01
@@ -352,6 +367,18 @@ def lib():
     L.acl_fleet_episode_batch.argtypes = [ct.POINTER(Formations), ct.POINTER(FleetEpisodeArgs),
                                           VP]
     L.acl_fleet_episode_batch.restype = ct.c_int
+    L.acl_fleet_delay_episode_workspace_bytes.argtypes = [I32, I32, I32, I32]
+    L.acl_fleet_delay_episode_workspace_bytes.restype = SZ
+    L.acl_fleet_delay_episode_batch.argtypes = [ct.POINTER(Formations),
+                                                ct.POINTER(FleetDelayEpisodeArgs), VP]
+    L.acl_fleet_delay_episode_batch.restype = ct.c_int
+    L.acl_fleet_delay_trial_workspace_bytes.argtypes = [I32, I32, I32, I32]
+    L.acl_fleet_delay_trial_workspace_bytes.restype = SZ
+    L.acl_fleet_delay_trial_init.argtypes = [ct.POINTER(FleetDelayTrialArgs), I32, VP]
+    L.acl_fleet_delay_trial_init.restype = ct.c_int
+    L.acl_fleet_delay_trial_batch.argtypes = [ct.POINTER(Formations),
+                                              ct.POINTER(FleetDelayTrialArgs), VP]
+    L.acl_fleet_delay_trial_batch.restype = ct.c_int
     L.acl_write_assignment_log.argtypes = [ct.c_char_p, I32, VP, VP, VP, VP, VP, VP]
     L.acl_write_assignment_log.restype = ct.c_int
     L.acl_read_assignment_log.argtypes = [ct.c_char_p, ct.POINTER(I32), VP, VP, VP, VP, VP, VP]

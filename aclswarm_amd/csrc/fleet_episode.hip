@@ -30,8 +30,17 @@
 // fleet_handoff_kernel launch (before any tick): the fleet kernel sees fidx
 // -1 for it, the control kernels a BAD_INPUT status, traj_kernel its skip
 // flag -- nothing of the swarm's state is written.
+//
+// acl_fleet_delay_episode_batch is the same loop (fep_run) with the step's
+// ticks those of acl_fleet_delay_auction_batch on the delay workspace layout:
+// per-link latency lat[b][w][u] in ticks. The first hand-off launch checks the
+// swarm's latency matrix too (n^2 bytes, folded into the row check's one
+// __syncthreads_or), so a swarm with a bad entry is skipped like one with a
+// bad row. Nothing else differs: what is in flight lives in the fleet
+// kernel's publication logs, which the loop never touches.
 #include "common.h"
 #include "episode_dev.h"
+#include "fleet_dev.h"  // kFleetMaxLat
 
 #include "../../include/aclswarm_amd.h"
 
@@ -49,11 +58,14 @@ struct FepLayout {
   size_t fleet, ctl, cst, u, us, ca, cmd, vf, fidx, skip, total;
 };
 
-inline FepLayout fep_layout(int n, int B, int cap) {
+// max_lat 0: acl_fleet_auction_batch's fleet part, else the delay layout's
+inline FepLayout fep_layout(int n, int B, int cap, int max_lat = 0) {
   FepLayout L;
   const size_t nb = (size_t)n, bb = (size_t)B;
   size_t o = 0;
-  L.fleet = o; o = ws_al(o + acl_fleet_workspace_bytes(n, B, cap));
+  L.fleet = o;
+  o = ws_al(o + (max_lat ? acl_fleet_delay_workspace_bytes(n, B, cap, max_lat)
+                         : acl_fleet_workspace_bytes(n, B, cap)));
   L.ctl = o;   o = ws_al(o + ws_layout(n, B).total);
   L.cst = o;   o = ws_al(o + bb * sizeof(acl_swarm_status_t));
   L.u = o;     o = ws_al(o + bb * nb * 3 * 8);
@@ -88,6 +100,8 @@ struct FepArgs {
   uint8_t* ctlMode;
   uint16_t* ctlRows;
   acl_swarm_status_t* cst;
+  const uint8_t* lat;  // [B][n][n] receiver-major; the delay entry only
+  int max_lat;
 };
 
 // CoordinationROS::autoauctionCb of every vehicle (coordination_ros.cpp:
@@ -127,7 +141,9 @@ __global__ void __launch_bounds__(kFepMaxN) fleet_cmd_kernel(const FepArgs A) {
 // kFirst (the call's first launch, before any tick): the swarm's input check
 // and its hand-off from the rows alone. Otherwise (after each step's ticks):
 // the flags of the step, and the hand-off again when a vehicle adopted.
-template <bool kFirst>
+// kLat (with kFirst, the delay entry): the swarm's latency matrix is part of
+// the input check.
+template <bool kFirst, bool kLat = false>
 __global__ void __launch_bounds__(kFepBlock) fleet_handoff_kernel(const FepArgs A) {
   __shared__ int cnt_s[3];
   const int b = (int)blockIdx.x, tid = (int)threadIdx.x, n = A.n;
@@ -168,6 +184,14 @@ __global__ void __launch_bounds__(kFepBlock) fleet_handoff_kernel(const FepArgs 
       if ((((unsigned long long)w1 << 32) | w0) != full0 ||
           (((unsigned long long)w3 << 32) | w2) != full1)
         bad = true;
+    }
+    if constexpr (kLat) {
+      // every off-diagonal entry in 1..max_lat, as the fleet kernel requires
+      const uint8_t* latb = A.lat + vb * n;
+      for (int k = tid; k < n * n; k += kFepBlock) {
+        const int w = k / n, l = latb[k];
+        if (k - w * n != w && (l < 1 || l > A.max_lat)) bad = true;
+      }
     }
     bad = __syncthreads_or(bad) != 0;
     if (tid == 0) {
@@ -266,37 +290,55 @@ extern "C" size_t acl_fleet_episode_workspace_bytes(int32_t n, int32_t B, int32_
   return acl_amd::fep_layout(n, B, queue_cap).total;
 }
 
-extern "C" acl_status_t acl_fleet_episode_batch(const acl_formations_t* F,
-                                                const acl_fleet_episode_args_t* a, void* stream) {
+extern "C" size_t acl_fleet_delay_episode_workspace_bytes(int32_t n, int32_t B, int32_t queue_cap,
+                                                          int32_t max_lat) {
   using namespace acl_amd;
-  if (!F || !a) return acl__set_error("acl_fleet_episode_batch: null argument");
+  if (n < 1 || n > kFepMaxN || B < 1 || queue_cap < 1 || max_lat < 1 || max_lat > kFleetMaxLat)
+    return 0;
+  return fep_layout(n, B, queue_cap, max_lat).total;
+}
+
+namespace {
+
+// The host loop of both entries. delay: the ticks are
+// acl_fleet_delay_auction_batch's under (lat, max_lat) on the delay workspace
+// layout; otherwise acl_fleet_auction_batch's, and lat / max_lat are unused.
+acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
+                     const acl_fleet_episode_args_t* a, const uint8_t* lat, int max_lat,
+                     void* stream) {
+  using namespace acl_amd;
+  static char msg[200];
+  auto fail = [&](const char* what) {
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return acl__set_error(msg);
+  };
+  if (!F || !a) return fail("null argument");
   const int n = F->n, B = a->B;
-  if (n < 1 || n > kFepMaxN)
-    return acl__set_error("acl_fleet_episode_batch: n out of range [1, 128]");
-  if (B < 0 || a->steps < 0 || a->step0 < 0)
-    return acl__set_error("acl_fleet_episode_batch: B, steps and step0 must be >= 0");
-  if (a->ticks_per_step < 1)
-    return acl__set_error("acl_fleet_episode_batch: ticks_per_step < 1");
-  if (a->max_iter < 0) return acl__set_error("acl_fleet_episode_batch: max_iter < 0");
-  if (a->queue_cap < 1) return acl__set_error("acl_fleet_episode_batch: queue_cap < 1");
+  if (n < 1 || n > kFepMaxN) return fail("n out of range [1, 128]");
+  if (B < 0 || a->steps < 0 || a->step0 < 0) return fail("B, steps and step0 must be >= 0");
+  if (a->ticks_per_step < 1) return fail("ticks_per_step < 1");
+  if (a->max_iter < 0) return fail("max_iter < 0");
+  if (a->queue_cap < 1) return fail("queue_cap < 1");
   const acl_episode_params_t& ep = a->ep;
   if (ep.auction_latency != 0 || ep.assignment != ACL_ASSIGN_CBAA)
-    return acl__set_error("acl_fleet_episode_batch: ep.auction_latency and ep.assignment must "
-                          "be 0 (the auction takes the time its messages take)");
+    return fail("ep.auction_latency and ep.assignment must be 0 (the auction takes the time its "
+                "messages take)");
   if (ep.auction_every < 1 || ep.sample_every < 1 || ep.bufflen < 1 || !(ep.control_dt > 0.0))
-    return acl__set_error("acl_fleet_episode_batch: auction_every, sample_every, bufflen must "
-                          "be >= 1 and control_dt > 0");
+    return fail("auction_every, sample_every, bufflen must be >= 1 and control_dt > 0");
+  if (delay && (max_lat < 1 || max_lat > kFleetMaxLat)) return fail("max_lat out of range [1, 64]");
+  if (!delay) max_lat = 0;
   if (B == 0 || a->steps == 0) return ACL_OK;
   if (!a->fidx || !a->q || !a->vel || !a->P || !a->Pt || !a->open || !a->invalid ||
       !a->just_received || !a->biditer || !a->price || !a->who || !a->Rt || !a->final_price ||
       !a->final_who || !a->done_tick || !a->vflags || !a->n_thrown || !a->n_tally ||
       !a->queue_len || !a->status || !a->adopt_step || !a->est || !a->ring_u || !a->ring_ca ||
       !a->fst || !a->workspace)
-    return acl__set_error("acl_fleet_episode_batch: required pointer is NULL");
-  if (a->workspace_bytes < acl_fleet_episode_workspace_bytes(n, B, a->queue_cap))
-    return acl__set_error("acl_fleet_episode_batch: workspace_bytes is too small "
-                          "(acl_fleet_episode_workspace_bytes)");
-  const FepLayout W = fep_layout(n, B, a->queue_cap);
+    return fail("required pointer is NULL");
+  if (delay && !lat) return fail("lat is NULL");
+  const FepLayout W = fep_layout(n, B, a->queue_cap, max_lat);
+  if (a->workspace_bytes < W.total)
+    return fail(delay ? "workspace_bytes is too small (acl_fleet_delay_episode_workspace_bytes)"
+                      : "workspace_bytes is too small (acl_fleet_episode_workspace_bytes)");
   const WsLayout WS = ws_layout(n, B);
   unsigned char* ws = (unsigned char*)a->workspace;
   unsigned char* wc = ws + W.ctl;  // the control stage's hand-off region
@@ -318,10 +360,13 @@ extern "C" acl_status_t acl_fleet_episode_batch(const acl_formations_t* F,
   A.ctlMode = wc + WS.mode;
   A.ctlRows = reinterpret_cast<uint16_t*>(wc + WS.rows);
   A.cst = reinterpret_cast<acl_swarm_status_t*>(ws + W.cst);
+  A.lat = lat; A.max_lat = max_lat;
 
   // the ticks: the fleet kernel on the episode's state; its vflags are the
   // step's own (A.vf, cleared by the hand-off), the caller's stay sticky
-  acl_fleet_auction_args_t fa = {};
+  acl_fleet_delay_args_t fd = {};
+  fd.lat = lat; fd.max_lat = max_lat;
+  acl_fleet_auction_args_t& fa = fd.base;
   fa.B = B; fa.ticks = a->ticks_per_step; fa.max_iter = a->max_iter; fa.queue_cap = a->queue_cap;
   fa.fidx = fidx_eff; fa.q = a->q; fa.Pt = a->Pt; fa.open = a->open; fa.invalid = a->invalid;
   fa.just_received = a->just_received; fa.biditer = a->biditer; fa.price = a->price;
@@ -329,7 +374,8 @@ extern "C" acl_status_t acl_fleet_episode_batch(const acl_formations_t* F,
   fa.done_tick = a->done_tick; fa.vflags = A.vf; fa.n_thrown = a->n_thrown;
   fa.n_tally = a->n_tally; fa.queue_len = a->queue_len; fa.status = a->status;
   fa.workspace = ws + W.fleet;
-  fa.workspace_bytes = acl_fleet_workspace_bytes(n, B, a->queue_cap);
+  fa.workspace_bytes = delay ? acl_fleet_delay_workspace_bytes(n, B, a->queue_cap, max_lat)
+                             : acl_fleet_workspace_bytes(n, B, a->queue_cap);
 
   acl_control_args_t cs = {};
   cs.B = B; cs.fidx = fidx_eff; cs.q = a->q; cs.vel = a->vel; cs.P = a->P;
@@ -353,7 +399,10 @@ extern "C" acl_status_t acl_fleet_episode_batch(const acl_formations_t* F,
       return acl__set_error("hipMemsetAsync failed");
   }
   // the call's input check and its hand-off from the rows alone
-  hipLaunchKernelGGL(fleet_handoff_kernel<true>, dim3(B), dim3(kFepBlock), 0, s, A);
+  if (delay)
+    hipLaunchKernelGGL((fleet_handoff_kernel<true, true>), dim3(B), dim3(kFepBlock), 0, s, A);
+  else
+    hipLaunchKernelGGL(fleet_handoff_kernel<true>, dim3(B), dim3(kFepBlock), 0, s, A);
   if (hipGetLastError() != hipSuccess)
     return acl__set_error("fleet_handoff_kernel launch failed");
   for (int k = 0; k < a->steps; ++k) {
@@ -367,7 +416,8 @@ extern "C" acl_status_t acl_fleet_episode_batch(const acl_formations_t* F,
         return acl__set_error("fleet_cmd_kernel launch failed");
     }
     fa.cmd = auction ? cmd : nullptr;
-    acl_status_t r = acl_fleet_auction_batch(F, &fa, stream);
+    acl_status_t r = delay ? acl_fleet_delay_auction_batch(F, &fd, stream)
+                           : acl_fleet_auction_batch(F, &fa, stream);
     if (r != ACL_OK) return r;
     hipLaunchKernelGGL(fleet_handoff_kernel<false>, dim3(B), dim3(kFepBlock), 0, s, A);
     if (hipGetLastError() != hipSuccess)
@@ -381,4 +431,18 @@ extern "C" acl_status_t acl_fleet_episode_batch(const acl_formations_t* F,
     if (hipGetLastError() != hipSuccess) return acl__set_error("traj_kernel launch failed");
   }
   return ACL_OK;
+}
+
+}  // namespace
+
+extern "C" acl_status_t acl_fleet_episode_batch(const acl_formations_t* F,
+                                                const acl_fleet_episode_args_t* a, void* stream) {
+  return fep_run("acl_fleet_episode_batch", false, F, a, nullptr, 0, stream);
+}
+
+extern "C" acl_status_t acl_fleet_delay_episode_batch(const acl_formations_t* F,
+                                                      const acl_fleet_delay_episode_args_t* d,
+                                                      void* stream) {
+  if (!d) return acl__set_error("acl_fleet_delay_episode_batch: null argument");
+  return fep_run("acl_fleet_delay_episode_batch", true, F, &d->base, d->lat, d->max_lat, stream);
 }

@@ -36,6 +36,15 @@
 // One workgroup per swarm in the new kernels; all are O(n) .. O(n^2) integer
 // work per swarm and latency-bound.
 //
+// acl_fleet_delay_trial_init / acl_fleet_delay_trial_batch are the same host
+// loops (ftr_init, ftr_run) with the step's ticks those of
+// acl_fleet_delay_auction_batch on the delay workspace layout: per-link
+// latency lat[b][w][u] in ticks. Two kernels differ, each in an instantiation
+// of its own: the first hand-off launch checks the swarm's latency matrix too
+// (n^2 bytes, folded into the row check's one __syncthreads_or), and the pre
+// kernel's commit acts on the delay layout, where what is in flight lives in
+// the publication logs and nothing is copied aside.
+//
 // Compiled with -ffp-contract=off (trial_dev.h).
 #include "common.h"
 #include "fleet_dev.h"
@@ -56,11 +65,13 @@ struct FtrLayout {
   size_t fleet, ctl, cst, u, us, ca, cmd, vf, fidx, skip, zstep, total;
 };
 
-inline FtrLayout ftr_layout(int n, int B, int cap) {
+// R 0: acl_fleet_auction_batch's fleet part, else the delay layout's with
+// publication logs of R entries
+inline FtrLayout ftr_layout(int n, int B, int cap, int R = 0) {
   FtrLayout L;
   const size_t nb = (size_t)n, bb = (size_t)B;
   size_t o = 0;
-  L.fleet = o; o = ws_al(o + (size_t)B * fleet_layout(n, cap).total);
+  L.fleet = o; o = ws_al(o + (size_t)B * fleet_layout(n, cap, R).total);
   L.ctl = o;   o = ws_al(o + ws_layout(n, B).total);
   L.cst = o;   o = ws_al(o + bb * sizeof(acl_swarm_status_t));
   L.u = o;     o = ws_al(o + bb * nb * 3 * 8);
@@ -106,6 +117,8 @@ struct FtrArgs {
   uint16_t* ctlRows;
   acl_swarm_status_t* cst;
   unsigned char* fleet_ws;
+  const uint8_t* lat;  // [B][n][n] receiver-major; the delay entries only
+  int max_lat;         // (0 otherwise)
 };
 
 // the arrays acl_fleet_trial_init alone writes
@@ -186,6 +199,8 @@ __global__ void __launch_bounds__(kFtrBlock) fleet_trial_init_kernel(const Trial
 // trial_pre_kernel's decisions (every thread: uniform), then the per-vehicle
 // work: a wave per vehicle for setFormation, lane l owning tasks l and l + 64
 // as in the fleet kernel; a thread per vehicle for the commands.
+// kDelay: the fleet workspace is the delay layout (acl_fleet_delay_trial_batch).
+template <bool kDelay>
 __global__ void __launch_bounds__(kFtrBlock) fleet_trial_pre_kernel(const FtrArgs A) {
   __shared__ int cnt_s[3];
   const int b = (int)blockIdx.x, tid = (int)threadIdx.x, n = A.n;
@@ -237,15 +252,38 @@ __global__ void __launch_bounds__(kFtrBlock) fleet_trial_pre_kernel(const FtrArg
     // Auctioneer::setFormation of every vehicle, open or not: reset(), the
     // identity row, formation_just_received_. bids_zero_, rxbids_ and
     // invalid_assignment_ are kept (auctioneer.cpp:42-62 clears none of them).
-    const FleetLayout L = fleet_layout(n, A.cap);
+    // On the delay layout every publication is in its sender's log by copy
+    // and stays there: nothing is copied aside (the layout has no stale
+    // table, and FleetMeta.live / stale are unused), and a bid in flight is
+    // delivered when due to whoever subscribes to its sender under the
+    // identity row.
+    const FleetLayout L = fleet_layout(n, A.cap, kDelay ? fleet_log_len(A.max_lat) : 0);
     unsigned char* ws = A.fleet_ws + (size_t)b * L.total;
     FleetMeta* meta_g = reinterpret_cast<FleetMeta*>(ws + L.meta);
     float* stale_g = reinterpret_cast<float*>(ws + L.stale);
     const size_t tw = 2 * (size_t)n;  // a table in 4-byte words
     for (int v = wv; v < n; v += kFtrBlock / 64) {
-      FleetMeta m = meta_g[v];
       float* pr = A.price + (vb + v) * n;
       int32_t* wh = A.who + (vb + v) * n;
+      if constexpr (kDelay) {
+        // only the bucket masks of the vehicle's bookkeeping change
+        fleet_clear_table<2>(pr, wh, n, lane);
+        uint16_t* row = A.Pt + (vb + v) * n;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const int j = lane + 64 * s;
+          if (j < n) row[j] = (uint16_t)j;
+        }
+        if (lane == 0) {
+          FleetMeta* mg = meta_g + v;
+          mg->mc[0] = mg->mc[1] = mg->mn[0] = mg->mn[1] = 0ull;
+          A.open[vb + v] = 0;
+          A.biditer[vb + v] = 0;
+          A.just_received[vb + v] = 1;
+        }
+        continue;
+      }
+      FleetMeta m = meta_g[v];
       if (m.live) {
         // the bid in flight outlives the table it was read from, as at a START
         // or FLUSH command. The stale slot is free: every step runs at least
@@ -328,7 +366,9 @@ __global__ void __launch_bounds__(kFtrBlock) fleet_trial_pre_kernel(const FtrArg
 // and its hand-off from the rows alone. Otherwise (after each step's ticks):
 // the flags of the step, the controller starts, vehicle 0's message, and the
 // hand-off again when a vehicle adopted.
-template <bool kFirst>
+// kLat (with kFirst, the delay entry): the swarm's latency matrix is part of
+// the input check.
+template <bool kFirst, bool kLat = false>
 __global__ void __launch_bounds__(kFtrBlock) fleet_trial_handoff_kernel(const FtrArgs A) {
   __shared__ int cnt_s[3];
   __shared__ int adopt0_s;
@@ -369,6 +409,14 @@ __global__ void __launch_bounds__(kFtrBlock) fleet_trial_handoff_kernel(const Ft
       if ((((unsigned long long)w1 << 32) | w0) != full0 ||
           (((unsigned long long)w3 << 32) | w2) != full1)
         bad = true;
+    }
+    if constexpr (kLat) {
+      // every off-diagonal entry in 1..max_lat, as the fleet kernel requires
+      const uint8_t* latb = A.lat + vb * n;
+      for (int k = tid; k < n * n; k += kFtrBlock) {
+        const int w = k / n, l = latb[k];
+        if (k - w * n != w && (l < 1 || l > A.max_lat)) bad = true;
+      }
     }
     bad = __syncthreads_or(bad) != 0;
     if (tid == 0) {
@@ -478,7 +526,34 @@ extern "C" size_t acl_fleet_trial_workspace_bytes(int32_t n, int32_t B, int32_t 
   return acl_amd::ftr_layout(n, B, queue_cap).total;
 }
 
+extern "C" size_t acl_fleet_delay_trial_workspace_bytes(int32_t n, int32_t B, int32_t queue_cap,
+                                                        int32_t max_lat) {
+  using namespace acl_amd;
+  if (n < 1 || n > kFleetMaxN || B < 1 || queue_cap < 1 || max_lat < 1 || max_lat > kFleetMaxLat)
+    return 0;
+  return ftr_layout(n, B, queue_cap, fleet_log_len(max_lat)).total;
+}
+
 namespace {
+
+// What distinguishes the delay entries: the latency matrix, and R, the length
+// of a vehicle's publication log (0: the entries without latency).
+struct FtrDelay {
+  const uint8_t* lat;
+  int max_lat, R;
+};
+constexpr FtrDelay kNoDelay = {nullptr, 0, 0};
+
+// (after ftr_check; before anything else reads max_lat)
+acl_status_t ftr_delay(const acl_fleet_delay_trial_args_t* d, const char* who, FtrDelay* out) {
+  static char msg[200];
+  if (d->max_lat < 1 || d->max_lat > acl_amd::kFleetMaxLat) {
+    snprintf(msg, sizeof(msg), "%s: max_lat out of range [1, 64]", who);
+    return acl__set_error(msg);
+  }
+  *out = FtrDelay{d->lat, d->max_lat, acl_amd::fleet_log_len(d->max_lat)};
+  return ACL_OK;
+}
 
 // the argument errors of both entry points that need no pointer
 acl_status_t ftr_check(const acl_fleet_trial_args_t* a, int n, const char* who) {
@@ -506,7 +581,8 @@ acl_status_t ftr_check(const acl_fleet_trial_args_t* a, int n, const char* who) 
   return ACL_OK;
 }
 
-acl_status_t ftr_pointers(const acl_fleet_trial_args_t* a, int n, const char* who) {
+acl_status_t ftr_pointers(const acl_fleet_trial_args_t* a, int n, const char* who,
+                          const FtrDelay& dl) {
   static char msg[200];
   auto fail = [&](const char* what) {
     snprintf(msg, sizeof(msg), "%s: %s", who, what);
@@ -519,14 +595,16 @@ acl_status_t ftr_pointers(const acl_fleet_trial_args_t* a, int n, const char* wh
       !a->n_thrown || !a->n_tally || !a->queue_len || !a->status || !a->adopt_step || !a->fst ||
       !a->workspace)
     return fail("required pointer is NULL");
-  if (a->workspace_bytes < acl_fleet_trial_workspace_bytes(n, a->B, a->queue_cap))
-    return fail("workspace_bytes is too small (acl_fleet_trial_workspace_bytes)");
+  if (dl.R && !dl.lat) return fail("lat is NULL");
+  if (a->workspace_bytes < acl_amd::ftr_layout(n, a->B, a->queue_cap, dl.R).total)
+    return fail(dl.R ? "workspace_bytes is too small (acl_fleet_delay_trial_workspace_bytes)"
+                     : "workspace_bytes is too small (acl_fleet_trial_workspace_bytes)");
   return ACL_OK;
 }
 
-acl_amd::TrialDev ftr_trial_dev(const acl_fleet_trial_args_t* a, int n) {
+acl_amd::TrialDev ftr_trial_dev(const acl_fleet_trial_args_t* a, int n, const FtrDelay& dl) {
   using namespace acl_amd;
-  const FtrLayout W = ftr_layout(n, a->B, a->queue_cap);
+  const FtrLayout W = ftr_layout(n, a->B, a->queue_cap, dl.R);
   const WsLayout WS = ws_layout(n, a->B);
   unsigned char* ws = (unsigned char*)a->workspace;
   unsigned char* wc = ws + W.ctl;
@@ -552,9 +630,10 @@ acl_amd::TrialDev ftr_trial_dev(const acl_fleet_trial_args_t* a, int n) {
   return D;
 }
 
-acl_amd::FtrArgs ftr_args(const acl_fleet_trial_args_t* a, int n, const acl_amd::TrialDev& D) {
+acl_amd::FtrArgs ftr_args(const acl_fleet_trial_args_t* a, int n, const acl_amd::TrialDev& D,
+                          const FtrDelay& dl) {
   using namespace acl_amd;
-  const FtrLayout W = ftr_layout(n, a->B, a->queue_cap);
+  const FtrLayout W = ftr_layout(n, a->B, a->queue_cap, dl.R);
   unsigned char* ws = (unsigned char*)a->workspace;
   FtrArgs A = {};
   A.n = n; A.B = a->B; A.K = a->K; A.step = a->step0; A.cap = a->queue_cap;
@@ -571,21 +650,20 @@ acl_amd::FtrArgs ftr_args(const acl_fleet_trial_args_t* a, int n, const acl_amd:
   A.status = a->status; A.fst = a->fst;
   A.ctlPt = D.ctlPt; A.ctlMode = D.ctlMode; A.ctlRows = D.ctlRows; A.cst = D.cst;
   A.fleet_ws = ws + W.fleet;
+  A.lat = dl.lat; A.max_lat = dl.max_lat;
   return A;
 }
 
-}  // namespace
-
-extern "C" acl_status_t acl_fleet_trial_init(const acl_fleet_trial_args_t* a, int32_t n,
-                                             void* stream) {
+// acl_fleet_trial_init and acl_fleet_delay_trial_init (after ftr_check): the
+// same kernel; the zero-filled workspace is the entry's own layout.
+acl_status_t ftr_init(const char* who, const acl_fleet_trial_args_t* a, int n, const FtrDelay& dl,
+                      void* stream) {
   using namespace acl_amd;
-  acl_status_t r = ftr_check(a, n, "acl_fleet_trial_init");
-  if (r != ACL_OK) return r;
   if (a->B == 0) return ACL_OK;
-  r = ftr_pointers(a, n, "acl_fleet_trial_init");
+  const acl_status_t r = ftr_pointers(a, n, who, dl);
   if (r != ACL_OK) return r;
-  const TrialDev D = ftr_trial_dev(a, n);
-  const FtrArgs A = ftr_args(a, n, D);
+  const TrialDev D = ftr_trial_dev(a, n, dl);
+  const FtrArgs A = ftr_args(a, n, D, dl);
   FtrInit I;
   I.Rt = a->Rt; I.final_price = a->final_price; I.final_who = a->final_who;
   I.done_tick = a->done_tick; I.n_thrown = a->n_thrown; I.n_tally = a->n_tally;
@@ -593,7 +671,8 @@ extern "C" acl_status_t acl_fleet_trial_init(const acl_fleet_trial_args_t* a, in
   hipStream_t s = (hipStream_t)stream;
   // freshly constructed auctioneers: empty queues and buckets, nothing in
   // flight, tick 0 (and the CA counter, the hand-off region, the step's flags)
-  if (hipMemsetAsync(a->workspace, 0, ftr_layout(n, a->B, a->queue_cap).total, s) != hipSuccess)
+  if (hipMemsetAsync(a->workspace, 0, ftr_layout(n, a->B, a->queue_cap, dl.R).total, s) !=
+      hipSuccess)
     return acl__set_error("hipMemsetAsync failed");
   hipLaunchKernelGGL(fleet_trial_init_kernel, dim3(a->B), dim3(kFtrBlock), 0, s, D, A, I);
   if (hipGetLastError() != hipSuccess)
@@ -601,29 +680,36 @@ extern "C" acl_status_t acl_fleet_trial_init(const acl_fleet_trial_args_t* a, in
   return ACL_OK;
 }
 
-extern "C" acl_status_t acl_fleet_trial_batch(const acl_formations_t* F,
-                                              const acl_fleet_trial_args_t* a, void* stream) {
+// The host loop of acl_fleet_trial_batch and acl_fleet_delay_trial_batch (after
+// ftr_check). With dl.R the ticks are acl_fleet_delay_auction_batch's under
+// (dl.lat, dl.max_lat) on the delay workspace layout.
+acl_status_t ftr_run(const char* who, const acl_formations_t* F, const acl_fleet_trial_args_t* a,
+                     const FtrDelay& dl, void* stream) {
   using namespace acl_amd;
-  if (!F) return acl__set_error("acl_fleet_trial_batch: null argument");
   const int n = F->n;
-  acl_status_t r = ftr_check(a, n, "acl_fleet_trial_batch");
-  if (r != ACL_OK) return r;
   const int B = a->B;
   if (B == 0 || a->steps == 0) return ACL_OK;
-  r = ftr_pointers(a, n, "acl_fleet_trial_batch");
+  acl_status_t r = ftr_pointers(a, n, who, dl);
   if (r != ACL_OK) return r;
-  if (F->n_formations < 1) return acl__set_error("acl_fleet_trial_batch: n_formations < 1");
-  const FtrLayout W = ftr_layout(n, B, a->queue_cap);
+  if (F->n_formations < 1) {
+    static char msg[200];
+    snprintf(msg, sizeof(msg), "%s: n_formations < 1", who);
+    return acl__set_error(msg);
+  }
+  const bool delay = dl.R != 0;
+  const FtrLayout W = ftr_layout(n, B, a->queue_cap, dl.R);
   unsigned char* ws = (unsigned char*)a->workspace;
   hipStream_t s = (hipStream_t)stream;
-  TrialDev D = ftr_trial_dev(a, n);
+  TrialDev D = ftr_trial_dev(a, n, dl);
   D.F = F->n_formations;
-  FtrArgs A = ftr_args(a, n, D);
+  FtrArgs A = ftr_args(a, n, D, dl);
   A.F = F->n_formations;
 
   // the ticks: the fleet kernel on the trial's state; its vflags are the
   // step's own (A.vf, cleared by the hand-off), the caller's stay sticky
-  acl_fleet_auction_args_t fa = {};
+  acl_fleet_delay_args_t fd = {};
+  fd.lat = dl.lat; fd.max_lat = dl.max_lat;
+  acl_fleet_auction_args_t& fa = fd.base;
   fa.B = B; fa.ticks = a->ticks_per_step; fa.max_iter = a->max_iter; fa.queue_cap = a->queue_cap;
   fa.fidx = A.fidx_eff; fa.q = a->q; fa.cmd = A.cmd; fa.Pt = a->Pt; fa.open = a->open;
   fa.invalid = a->invalid; fa.just_received = a->just_received; fa.biditer = a->biditer;
@@ -632,7 +718,7 @@ extern "C" acl_status_t acl_fleet_trial_batch(const acl_formations_t* F,
   fa.n_thrown = a->n_thrown; fa.n_tally = a->n_tally; fa.queue_len = a->queue_len;
   fa.status = a->status;
   fa.workspace = ws + W.fleet;
-  fa.workspace_bytes = acl_fleet_workspace_bytes(n, B, a->queue_cap);
+  fa.workspace_bytes = (size_t)B * fleet_layout(n, a->queue_cap, dl.R).total;
 
   // the control stage on the current formations (a->fidx is in range for every
   // swarm the control kernels do not skip) and the hand-off region
@@ -647,17 +733,25 @@ extern "C" acl_status_t acl_fleet_trial_batch(const acl_formations_t* F,
     return acl__set_error("hipMemsetAsync failed");
 
   // the call's input check and its hand-off from the rows alone
-  hipLaunchKernelGGL(fleet_trial_handoff_kernel<true>, dim3(B), dim3(kFtrBlock), 0, s, A);
+  if (delay)
+    hipLaunchKernelGGL((fleet_trial_handoff_kernel<true, true>), dim3(B), dim3(kFtrBlock), 0, s,
+                       A);
+  else
+    hipLaunchKernelGGL(fleet_trial_handoff_kernel<true>, dim3(B), dim3(kFtrBlock), 0, s, A);
   if (hipGetLastError() != hipSuccess)
     return acl__set_error("fleet_trial_handoff_kernel launch failed");
   const acl_episode_params_t& ep = a->tp.ep;
   for (int k = 0; k < a->steps; ++k) {
     D.step = A.step = a->step0 + k;
     D.k = A.k = k;
-    hipLaunchKernelGGL(fleet_trial_pre_kernel, dim3(B), dim3(kFtrBlock), 0, s, A);
+    if (delay)
+      hipLaunchKernelGGL(fleet_trial_pre_kernel<true>, dim3(B), dim3(kFtrBlock), 0, s, A);
+    else
+      hipLaunchKernelGGL(fleet_trial_pre_kernel<false>, dim3(B), dim3(kFtrBlock), 0, s, A);
     if (hipGetLastError() != hipSuccess)
       return acl__set_error("fleet_trial_pre_kernel launch failed");
-    r = acl_fleet_auction_batch(F, &fa, stream);
+    r = delay ? acl_fleet_delay_auction_batch(F, &fd, stream)
+              : acl_fleet_auction_batch(F, &fa, stream);
     if (r != ACL_OK) return r;
     hipLaunchKernelGGL(fleet_trial_handoff_kernel<false>, dim3(B), dim3(kFtrBlock), 0, s, A);
     if (hipGetLastError() != hipSuccess)
@@ -672,4 +766,44 @@ extern "C" acl_status_t acl_fleet_trial_batch(const acl_formations_t* F,
     }
   }
   return ACL_OK;
+}
+
+}  // namespace
+
+extern "C" acl_status_t acl_fleet_trial_init(const acl_fleet_trial_args_t* a, int32_t n,
+                                             void* stream) {
+  static const char who[] = "acl_fleet_trial_init";
+  const acl_status_t r = ftr_check(a, n, who);
+  return r != ACL_OK ? r : ftr_init(who, a, n, kNoDelay, stream);
+}
+
+extern "C" acl_status_t acl_fleet_trial_batch(const acl_formations_t* F,
+                                              const acl_fleet_trial_args_t* a, void* stream) {
+  static const char who[] = "acl_fleet_trial_batch";
+  if (!F) return acl__set_error("acl_fleet_trial_batch: null argument");
+  const acl_status_t r = ftr_check(a, F->n, who);
+  return r != ACL_OK ? r : ftr_run(who, F, a, kNoDelay, stream);
+}
+
+extern "C" acl_status_t acl_fleet_delay_trial_init(const acl_fleet_delay_trial_args_t* d,
+                                                   int32_t n, void* stream) {
+  static const char who[] = "acl_fleet_delay_trial_init";
+  if (!d) return acl__set_error("acl_fleet_delay_trial_init: null argument");
+  acl_status_t r = ftr_check(&d->base, n, who);
+  if (r != ACL_OK) return r;
+  FtrDelay dl;
+  r = ftr_delay(d, who, &dl);
+  return r != ACL_OK ? r : ftr_init(who, &d->base, n, dl, stream);
+}
+
+extern "C" acl_status_t acl_fleet_delay_trial_batch(const acl_formations_t* F,
+                                                    const acl_fleet_delay_trial_args_t* d,
+                                                    void* stream) {
+  static const char who[] = "acl_fleet_delay_trial_batch";
+  if (!F || !d) return acl__set_error("acl_fleet_delay_trial_batch: null argument");
+  acl_status_t r = ftr_check(&d->base, F->n, who);
+  if (r != ACL_OK) return r;
+  FtrDelay dl;
+  r = ftr_delay(d, who, &dl);
+  return r != ACL_OK ? r : ftr_run(who, F, &d->base, dl, stream);
 }

@@ -782,14 +782,20 @@ class FleetEpisode:
     final_who, done_tick, vflags, n_thrown, n_tally, queue_len), adopt_step,
     the supervisor's rings and both status arrays. just_received starts at 1
     and adopt_step at -1; the caller may rewrite any state tensor between
-    runs. Raises ValueError on a malformed argument before anything runs."""
+    runs. Raises ValueError on a malformed argument before anything runs.
+
+    latency None: that entry exactly. Otherwise the episode runs
+    acl_fleet_delay_episode_batch: the steps' ticks are those of the fleet
+    auction with per-link latency, with latency and max_latency exactly as
+    FleetAuction takes them (an int, or a uint8 tensor [B][n][n],
+    receiver-major; fixed for the object's life)."""
 
     FLEET_KEYS = ("Pt", "open", "invalid", "just_received", "biditer", "price", "who", "Rt",
                   "final_price", "final_who", "done_tick", "vflags", "n_thrown", "n_tally",
                   "queue_len")
 
     def __init__(self, table, fidx, q, vel, Pt=None, params=None, cntrl=None, safety=None,
-                 queue_cap=None, max_iter=0, ticks_per_step=10):
+                 queue_cap=None, max_iter=0, ticks_per_step=10, latency=None, max_latency=None):
         n = table.n
         if n < 1 or n > L.FLEET_MAX_N:
             raise ValueError(f"FleetEpisode: n = {n} out of range [1, {L.FLEET_MAX_N}]")
@@ -815,6 +821,7 @@ class FleetEpisode:
             want["Pt"] = (Pt, torch.int16, (B, n, n))
         _check_state("FleetEpisode", table, want)
         dev = q.device
+        self.latency, self.max_latency = FleetAuction._latency(latency, max_latency, B, n, dev)
         if Pt is None:
             Pt = torch.arange(n, dtype=torch.int16, device=dev).repeat(B, n, 1)
         elif not torch.equal(torch.sort(Pt.to(torch.int32) & 0xFFFF, dim=2).values,
@@ -864,6 +871,9 @@ class FleetEpisode:
         self.step = 0
 
     def workspace_bytes(self):
+        if self.latency is not None:
+            return int(L.lib().acl_fleet_delay_episode_workspace_bytes(
+                self.n, self.B, self.queue_cap, self.max_latency))
         return int(L.lib().acl_fleet_episode_workspace_bytes(self.n, self.B, self.queue_cap))
 
     def run(self, steps, history=False, stream=None):
@@ -888,7 +898,8 @@ class FleetEpisode:
                 "P": torch.zeros((steps, B, n), dtype=torch.int16, device=dev),
                 "vflags": torch.zeros((steps, B, n), dtype=torch.int32, device=dev),
             }
-        a = L.FleetEpisodeArgs()
+        d = L.FleetDelayEpisodeArgs()
+        a = d.base if self.latency is not None else L.FleetEpisodeArgs()
         a.B, a.step0, a.steps, a.ticks_per_step = B, self.step, steps, self.ticks_per_step
         a.max_iter, a.queue_cap = self.max_iter, self.queue_cap
         for k in ("fidx", "q", "vel", "P", "adopt_step", "est", "ring_u", "ring_ca", "fst") + \
@@ -904,8 +915,15 @@ class FleetEpisode:
         F = self.table.struct()
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
-        L.check(L.lib().acl_fleet_episode_batch(ct.byref(F), ct.byref(a), ct.c_void_p(stream)),
-                "acl_fleet_episode_batch")
+        if self.latency is not None:
+            d.lat, d.max_lat = self.latency.data_ptr(), self.max_latency
+            L.check(L.lib().acl_fleet_delay_episode_batch(ct.byref(F), ct.byref(d),
+                                                          ct.c_void_p(stream)),
+                    "acl_fleet_delay_episode_batch")
+        else:
+            L.check(L.lib().acl_fleet_episode_batch(ct.byref(F), ct.byref(a),
+                                                    ct.c_void_p(stream)),
+                    "acl_fleet_episode_batch")
         self.step += steps
         return hist
 
@@ -1040,14 +1058,20 @@ class FleetTrial:
     queue_cap None: 4 n; max_iter 0: 2 n. The object owns the state: Trial's
     (q, vel, P, ts, ctl_on, the rings, posf and the records), FleetEpisode's
     fleet state, outputs, adopt_step and fst. Raises ValueError on a malformed
-    argument before anything is allocated."""
+    argument before anything is allocated.
+
+    latency None: that entry exactly. Otherwise the trials run
+    acl_fleet_delay_trial_init / acl_fleet_delay_trial_batch: the steps' ticks
+    are those of the fleet auction with per-link latency, with latency and
+    max_latency exactly as FleetAuction takes them (an int, or a uint8 tensor
+    [B][n][n], receiver-major; fixed for the object's life)."""
 
     TRIAL_KEYS = ("fseq", "fidx", "q", "vel", "P", "ts", "ctl_on", "ring_u", "ring_ca", "posf",
                   "dist", "t_conv", "t_avoid", "n_assign")
     FLEET_KEYS = FleetEpisode.FLEET_KEYS + ("adopt_step", "fst")
 
     def __init__(self, table, fseq, q, vel, params=None, cntrl=None, safety=None, queue_cap=None,
-                 max_iter=0, ticks_per_step=10):
+                 max_iter=0, ticks_per_step=10, latency=None, max_latency=None):
         n = table.n
         if n < 1 or n > L.FLEET_MAX_N:
             raise ValueError(f"FleetTrial: n = {n} out of range [1, {L.FLEET_MAX_N}]")
@@ -1071,6 +1095,7 @@ class FleetTrial:
                                            "vel": (vel, torch.float64, (B, n, 3)),
                                            "fseq": (fseq, torch.int32, (B, None))})
         dev = q.device
+        self.latency, self.max_latency = FleetAuction._latency(latency, max_latency, B, n, dev)
         self.table, self.n, self.B, self.device = table, n, B, dev
         self.K = K = int(fseq.shape[1])
         self.queue_cap, self.max_iter = int(queue_cap), int(max_iter)
@@ -1118,14 +1143,24 @@ class FleetTrial:
         self.ws = e((self.workspace_bytes(),), torch.uint8)
         self.step = 0
         a = self._args(0)
-        L.check(L.lib().acl_fleet_trial_init(ct.byref(a), n, ct.c_void_p(
-            torch.cuda.current_stream(dev).cuda_stream)), "acl_fleet_trial_init")
+        stream = ct.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        if self.latency is not None:
+            L.check(L.lib().acl_fleet_delay_trial_init(ct.byref(a), n, stream),
+                    "acl_fleet_delay_trial_init")
+        else:
+            L.check(L.lib().acl_fleet_trial_init(ct.byref(a), n, stream), "acl_fleet_trial_init")
 
     def workspace_bytes(self):
+        if self.latency is not None:
+            return int(L.lib().acl_fleet_delay_trial_workspace_bytes(
+                self.n, self.B, self.queue_cap, self.max_latency))
         return int(L.lib().acl_fleet_trial_workspace_bytes(self.n, self.B, self.queue_cap))
 
     def _args(self, steps, hist=None):
-        a = L.FleetTrialArgs()
+        """The entry's argument struct: FleetTrialArgs, or with latency the
+        FleetDelayTrialArgs around it."""
+        d = L.FleetDelayTrialArgs() if self.latency is not None else None
+        a = d.base if d is not None else L.FleetTrialArgs()
         a.B, a.K, a.step0, a.steps = self.B, self.K, self.step, steps
         a.ticks_per_step, a.max_iter, a.queue_cap = self.ticks_per_step, self.max_iter, \
             self.queue_cap
@@ -1138,6 +1173,9 @@ class FleetTrial:
         a.workspace = self.ws.data_ptr()
         a.workspace_bytes = self.ws.numel()
         a.cntrl, a.safety, a.tp = self.cntrl, self.safety, self.tp
+        if d is not None:
+            d.lat, d.max_lat = self.latency.data_ptr(), self.max_latency
+            return d
         return a
 
     def run(self, steps, history=False, stream=None):
@@ -1164,8 +1202,13 @@ class FleetTrial:
         F = self.table.struct()
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
-        L.check(L.lib().acl_fleet_trial_batch(ct.byref(F), ct.byref(a), ct.c_void_p(stream)),
-                "acl_fleet_trial_batch")
+        if self.latency is not None:
+            L.check(L.lib().acl_fleet_delay_trial_batch(ct.byref(F), ct.byref(a),
+                                                        ct.c_void_p(stream)),
+                    "acl_fleet_delay_trial_batch")
+        else:
+            L.check(L.lib().acl_fleet_trial_batch(ct.byref(F), ct.byref(a), ct.c_void_p(stream)),
+                    "acl_fleet_trial_batch")
         self.step += steps
         return hist
 

@@ -726,9 +726,10 @@ acl_status_t acl_fleet_auction_batch(const acl_formations_t* formations,
  * workspace_bytes too small. n in [1, 128]. Stream-ordered, never
  * synchronises.
  *
- * Not modelled: latencies that change over time, message loss, and latency in
- * acl_fleet_episode_batch / acl_fleet_trial_batch (which run the entry
- * above). */
+ * Not modelled: latencies that change over time and message loss. The closed
+ * loops on this entry are acl_fleet_delay_episode_batch and
+ * acl_fleet_delay_trial_batch (acl_fleet_episode_batch / acl_fleet_trial_batch
+ * run the entry above). */
 typedef struct {
   acl_fleet_auction_args_t base; /* workspace: acl_fleet_delay_workspace_bytes */
   const uint8_t* lat;            /* [B][n][n] receiver-major: lat[b][w][u], ticks from u to w */
@@ -1008,6 +1009,62 @@ typedef struct {
 size_t acl_fleet_episode_workspace_bytes(int32_t n, int32_t B, int32_t queue_cap);
 acl_status_t acl_fleet_episode_batch(const acl_formations_t* formations,
                                      const acl_fleet_episode_args_t* args, void* stream);
+
+/* ---- episodes with per-link message latency (added within ABI 11) ----------
+ * acl_fleet_delay_episode_batch is acl_fleet_episode_batch with step 2
+ * replaced: the step's ticks_per_step ticks are ticks of
+ * acl_fleet_delay_auction_batch on the delay workspace layout, with lat and
+ * max_lat handed back on every call. Everything else above holds. Added
+ * symbols: ACL_ABI_VERSION stays 11 (no existing struct or call changed).
+ *
+ * Time. Latency counts the workspace's tick counter (the one done_tick
+ * reports). A swarm with anything in flight is not quiescent, so every tick
+ * of a step runs while a bid is due: a bid published with publication tick P
+ * reaches receiver w exactly lat[b][w][u] auctioneer ticks later, across step
+ * and call boundaries, and may be in flight over up to 64 / ticks_per_step
+ * steps. (A quiescent swarm's counter stands still, as above.)
+ *
+ * Commands. The auto-auction commands are those of step 1. A START on an
+ * open auctioneer is a restart; bids in flight stay in flight through it, so
+ * the new auction files the old auction's START bids as they arrive and
+ * refuses its own neighbours' fresh ones (the first entry of a sender stays),
+ * as for acl_fleet_delay_auction_batch.
+ *
+ * Capacity. The publication log's argument carries over: every step is one
+ * call that runs at least one tick after its commands, a step issues at most
+ * one command per vehicle, so a sender publishes at most two bids per
+ * publication tick and the log of 2 max_lat bids never overwrites one in
+ * flight.
+ *
+ * Bad latency. A swarm whose lat holds an off-diagonal entry outside
+ * 1..max_lat is flagged ACL_FLEET_BAD_INPUT in fst by the call's first
+ * launch, before any tick, exactly like a row that is no permutation: no
+ * ticks, no control, its state unchanged, vflags_hist rows 0. The other
+ * swarms run.
+ *
+ * Workspace: acl_fleet_delay_episode_workspace_bytes(n, B, queue_cap,
+ * max_lat) bytes: the layout above with the fleet part sized by
+ * acl_fleet_delay_workspace_bytes; zero-filled once, handed back with the same
+ * n, B, queue_cap, lat and max_lat, and not interchangeable with a workspace
+ * of acl_fleet_episode_workspace_bytes. Argument errors: those of
+ * acl_fleet_episode_batch on `base`, plus lat NULL, max_lat outside 1..64,
+ * workspace_bytes too small. n in [1, 128].
+ *
+ * With every link at 1 tick this is acl_fleet_episode_batch step for step:
+ * the same state, outputs, histories and statuses.
+ * Not modelled: latencies that change over time, message loss; all model
+ * limits of acl_fleet_episode_batch but "latency below one tick" remain. */
+typedef struct {
+  acl_fleet_episode_args_t base; /* workspace: acl_fleet_delay_episode_workspace_bytes */
+  const uint8_t* lat;            /* [B][n][n] receiver-major, as acl_fleet_delay_args_t */
+  int32_t max_lat;               /* 1..64 */
+} acl_fleet_delay_episode_args_t;
+
+size_t acl_fleet_delay_episode_workspace_bytes(int32_t n, int32_t B, int32_t queue_cap,
+                                               int32_t max_lat);
+acl_status_t acl_fleet_delay_episode_batch(const acl_formations_t* formations,
+                                           const acl_fleet_delay_episode_args_t* args,
+                                           void* stream);
 
 /* ---- batched Monte-Carlo trials (ABI 9; SURVEY §8f widening of row f1) ---
  * B independent trials of aclswarm_sim's supervisor (aclswarm_sim/nodes/
@@ -1296,6 +1353,50 @@ size_t acl_fleet_trial_workspace_bytes(int32_t n, int32_t B, int32_t queue_cap);
 acl_status_t acl_fleet_trial_init(const acl_fleet_trial_args_t* args, int32_t n, void* stream);
 acl_status_t acl_fleet_trial_batch(const acl_formations_t* formations,
                                    const acl_fleet_trial_args_t* args, void* stream);
+
+/* ---- trials with per-link message latency (added within ABI 11) ------------
+ * acl_fleet_delay_trial_batch is acl_fleet_trial_batch with step 3 replaced:
+ * the step's ticks_per_step ticks are ticks of acl_fleet_delay_auction_batch
+ * on the delay workspace layout, with lat and max_lat handed back on every
+ * call. Time, commands, capacity, bad latency and the argument errors are
+ * those of acl_fleet_delay_episode_batch (a finished trial, a bad row and a
+ * bad latency matrix all leave their swarm untouched); everything else above
+ * holds. Added symbols: ACL_ABI_VERSION stays 11.
+ *
+ * Commit. Auctioneer::setFormation (auctioneer.cpp:42-62) of every vehicle on
+ * the delay layout: reset() (table cleared, current and next bucket masks
+ * cleared, open = 0, biditer = 0), the identity row, just_received = 1. The
+ * delay layout has no stale table and publications are in the sender's log
+ * by copy, so nothing is copied aside. The publication log, the START
+ * bucket, the queue, invalid, Rt, the start position, final_* and done_tick
+ * stay. A bid in flight is delivered when due if the receiver subscribes to
+ * the sender under its row at that moment -- now the identity. A commit
+ * publishes nothing, so the capacity argument is unchanged.
+ *
+ * acl_fleet_delay_trial_init is acl_fleet_trial_init on the delay workspace
+ * (zero-filled: empty logs, tick 0).
+ * Workspace: acl_fleet_delay_trial_workspace_bytes(n, B, queue_cap, max_lat)
+ * bytes: the layout above with the fleet part sized by
+ * acl_fleet_delay_workspace_bytes; not interchangeable with a workspace of
+ * acl_fleet_trial_workspace_bytes.
+ *
+ * With every link at 1 tick this is acl_fleet_trial_batch step for step.
+ * Not modelled: latencies that change over time, message loss, and latency on
+ * the supervisor's subscription to vehicle 0 (its message still arrives in the
+ * step of the adoption); all model limits of acl_fleet_trial_batch but
+ * "latency below one tick" remain. */
+typedef struct {
+  acl_fleet_trial_args_t base; /* workspace: acl_fleet_delay_trial_workspace_bytes */
+  const uint8_t* lat;          /* [B][n][n] receiver-major, as acl_fleet_delay_args_t */
+  int32_t max_lat;             /* 1..64 */
+} acl_fleet_delay_trial_args_t;
+
+size_t acl_fleet_delay_trial_workspace_bytes(int32_t n, int32_t B, int32_t queue_cap,
+                                             int32_t max_lat);
+acl_status_t acl_fleet_delay_trial_init(const acl_fleet_delay_trial_args_t* args, int32_t n,
+                                        void* stream);
+acl_status_t acl_fleet_delay_trial_batch(const acl_formations_t* formations,
+                                         const acl_fleet_delay_trial_args_t* args, void* stream);
 
 /* ---- random formation groups on the device -----------
  * Replaces aclswarm_sim/nodes/generate_random_formation.py:59-80

@@ -17,6 +17,10 @@ launch to quiescence) times the ticks the slowest swarm ran.
 Also recorded: how many of the started auctions reach consensus before the
 next auto-auction restarts them -- at large d_max the reference's own
 auctions (2 n d_max ticks of 1 ms) outlast its 1.2 s auto-auction period.
+
+With --latency L[,L...] a further loop per L is alternated with them: the same
+episodes on acl_fleet_delay_episode_batch with every link at L ticks
+(engine.FleetEpisode(latency=L)), reported under "delay".
 Writes one JSON document (--out)."""
 import argparse
 import json
@@ -53,7 +57,7 @@ def per_tick_us(n, B):
     return None
 
 
-def bench(n, B, F, steps, reps, warmup, dev):
+def bench(n, B, F, steps, reps, warmup, dev, latencies=()):
     gen = torch.Generator(device=dev)
     gen.manual_seed(500 + n)
     w = workload.simform_workload(B, n, gen, dev, F=F, complete=False, planes=5)
@@ -72,17 +76,29 @@ def bench(n, B, F, steps, reps, warmup, dev):
         fe.ws = ws.zero_()
         return timed(lambda: fe.run(steps), dev), fe
 
+    def delayed(ticks):
+        fe = engine.FleetEpisode(T, w["fidx"], w["q"], w["vel"], latency=ticks)
+        fe.run(0)  # (allocates the zero-filled workspace: not timed)
+        return timed(lambda: fe.run(steps), dev), fe
+
     def sync_episode():
         e = engine.Episode(T, w["fidx"], w["q"], w["vel"], w["P_in"], params=lat)
         return timed(lambda: e.run(steps), dev), e
 
     t_fleet, t_sync = [], []
+    t_delay, last_delay = {k: [] for k in latencies}, {}
     for r in range(warmup + reps):
         dt_f, fe = fleet()
         dt_s, e = sync_episode()
         if r >= warmup:
             t_fleet.append(dt_f)
             t_sync.append(dt_s)
+        for k in latencies:
+            dt_d, fd = delayed(k)
+            if r >= warmup:
+                t_delay[k].append(dt_d)
+            last_delay[k] = fd.status()["fleet"], fd.workspace_bytes()
+            del fd
     st = fe.status()
     fst, est = st["fleet"], e.status()
     assert (fst["flags"] == 0).all(), "a swarm overflowed or was refused"
@@ -90,7 +106,22 @@ def bench(n, B, F, steps, reps, warmup, dev):
     started, consensus = int(fst["n_started"].sum()), int(fst["n_consensus"].sum())
     ticks_max = int(fst["ticks_run"].max())
     us = per_tick_us(n, B)
+    delays = []
+    for k in latencies:
+        md = statistics.median(t_delay[k])
+        f, wsb = last_delay[k]
+        assert (f["flags"] == 0).all(), "a swarm overflowed or was refused"
+        delays.append(dict(
+            latency=k, delay_ms_per_step=md / steps * 1e3, delay_swarm_steps_per_s=B * steps / md,
+            delay_s_all=t_delay[k], delay_over_fleet=md / mf,
+            ticks_run_max=int(f["ticks_run"].max()), ticks_run_min=int(f["ticks_run"].min()),
+            vehicle_auctions_started=int(f["n_started"].sum()),
+            vehicle_auctions_restarted=int(f["n_restarted"].sum()),
+            vehicle_auctions_finished=int(f["n_consensus"].sum()),
+            vehicles_adopted=int(f["n_adopted"].sum()), vehicles_invalid=int(f["n_invalid"].sum()),
+            workspace_bytes=wsb))
     return dict(
+        delay=delays,
         n=n, B=B, formations=F, d_max=d_max, steps=steps, ticks_per_step=fe.ticks_per_step,
         auction_every=int(fe.ep.auction_every), queue_cap=fe.queue_cap,
         fleet_ms_per_step=mf / steps * 1e3, fleet_swarm_steps_per_s=B * steps / mf,
@@ -116,13 +147,16 @@ def main():
     ap.add_argument("--steps", type=int, default=240)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--latency", default="", help="uniform link latencies in ticks, "
+                                                  "comma-separated (default: none)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fleet_episode", "steps.json"))
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     res = []
     for s in a.shapes.split(","):
         n, B = (int(x) for x in s.split("x"))
-        r = bench(n, B, a.formations, a.steps, a.reps, a.warmup, dev)
+        r = bench(n, B, a.formations, a.steps, a.reps, a.warmup, dev,
+                  [int(x) for x in a.latency.split(",") if x])
         print(json.dumps(r), flush=True)
         res.append(r)
     doc = dict(device=torch.cuda.get_device_name(dev), reps=a.reps, warmup=a.warmup,

@@ -17,6 +17,10 @@ terminated from, time to converge, gridlock time and assignments per
 formation. For the new loop also the vehicle events: starts, restarts,
 flushes, and the vehicle auctions that ended neither in a restart nor in
 consensus, i.e. were interrupted by a commit or cut by the trial's end.
+
+With --latency L[,L...] a further loop per L is alternated with them: the same
+trials on acl_fleet_delay_trial_batch with every link at L ticks
+(engine.FleetTrial(latency=L)), reported as "fleet_L<L>" with the same figures.
 Writes one JSON document (--out)."""
 import argparse
 import json
@@ -53,7 +57,7 @@ def fly(make, max_steps, chunk, dev):
     return time.perf_counter() - t0, steps, tr
 
 
-def bench(n, B, reps, warmup, max_steps, chunk, dev):
+def bench(n, B, reps, warmup, max_steps, chunk, dev, latencies=()):
     L_side = 15.0 if n <= 20 else 40.0 * (n / 100.0) ** 0.5
     T, t_admm, admm = admm_table(n, B, L_side, 0, dev)
     gen = torch.Generator(device=dev)
@@ -64,6 +68,8 @@ def bench(n, B, reps, warmup, max_steps, chunk, dev):
     fseq = torch.arange(2 * B, dtype=torch.int32, device=dev).view(B, 2)
     loops = {"fleet": lambda: engine.FleetTrial(T, fseq, q, vel),
              "sync": lambda: engine.Trial(T, fseq, q, vel)}
+    for lat in latencies:
+        loops[f"fleet_L{lat}"] = lambda lat=lat: engine.FleetTrial(T, fseq, q, vel, latency=lat)
     times = {k: [] for k in loops}
     last = {}
     for r in range(warmup + reps):
@@ -84,7 +90,7 @@ def bench(n, B, reps, warmup, max_steps, chunk, dev):
         r = trial_stats(tr, 2)
         r.update(trials_per_s=B / m, seconds=m, seconds_all=times[k], steps_run=steps,
                  ms_per_step=m / steps * 1e3)
-        if k == "fleet":
+        if k.startswith("fleet"):
             f = tr.fleet_status()["fleet"]
             started, restarted = int(f["n_started"].sum()), int(f["n_restarted"].sum())
             consensus = int(f["n_consensus"].sum())
@@ -98,6 +104,10 @@ def bench(n, B, reps, warmup, max_steps, chunk, dev):
                      workspace_bytes=tr.workspace_bytes())
         out[k] = r
     out["fleet_over_sync_seconds"] = out["fleet"]["seconds"] / out["sync"]["seconds"]
+    for lat in latencies:
+        out[f"fleet_L{lat}"]["latency"] = lat
+        out[f"fleet_L{lat}_over_fleet_seconds"] = (out[f"fleet_L{lat}"]["seconds"] /
+                                                   out["fleet"]["seconds"])
     return out
 
 
@@ -108,13 +118,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--max-steps", type=int, default=12000)
     ap.add_argument("--chunk", type=int, default=500)
+    ap.add_argument("--latency", default="", help="uniform link latencies in ticks, "
+                                                  "comma-separated (default: none)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fleet_trial", "trials.json"))
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     res = []
     for s in a.shapes.split(","):
         n, B = (int(x) for x in s.split("x"))
-        r = bench(n, B, a.reps, a.warmup, a.max_steps, a.chunk, dev)
+        r = bench(n, B, a.reps, a.warmup, a.max_steps, a.chunk, dev,
+                  [int(x) for x in a.latency.split(",") if x])
         print(json.dumps(r), flush=True)
         res.append(r)
     doc = dict(device=torch.cuda.get_device_name(dev), reps=a.reps, warmup=a.warmup,

@@ -43,6 +43,8 @@ EXPORTS = (
     "acl_fleet_delay_episode_workspace_bytes", "acl_fleet_delay_episode_batch",
     "acl_fleet_delay_trial_workspace_bytes", "acl_fleet_delay_trial_init",
     "acl_fleet_delay_trial_batch",
+    "acl_fleet_lossy_auction_batch", "acl_fleet_lossy_episode_batch",
+    "acl_fleet_lossy_trial_batch",
     "acl_default_episode_params", "acl_episode_workspace_bytes", "acl_episode_batch",
     "acl_default_trial_params", "acl_trial_workspace_bytes", "acl_trial_init", "acl_trial_batch",
     "acl_fleet_trial_workspace_bytes", "acl_fleet_trial_init", "acl_fleet_trial_batch",
@@ -149,6 +151,21 @@ class FleetDelayArgs(ct.Structure):
     per-link message latency, lat [B][n][n] u8 receiver-major, in ticks."""
     _fields_ = [("base", FleetAuctionArgs), ("lat", ct.c_void_p), ("max_lat", ct.c_int32)]
 
+
+FLEET_LOSS_DEAD = 0xFFFF  # acl_fleet_loss_t::loss: a dead link
+
+
+class FleetLoss(ct.Structure):
+    """acl_fleet_loss_t (added within ABI 11): seeded per-link message loss,
+    loss [B][n][n] u16 receiver-major, seed [B] u32, n_lost [B][n] i32 in/out."""
+    _fields_ = [("loss", ct.c_void_p), ("seed", ct.c_void_p), ("n_lost", ct.c_void_p)]
+
+
+class FleetLossyArgs(ct.Structure):
+    """acl_fleet_lossy_args_t (added within ABI 11)."""
+    _fields_ = [("delay", FleetDelayArgs), ("link", FleetLoss)]
+
+
 FLEET_STATUS_DTYPE = np.dtype([(k, "<i4") for k in ("ticks_run", "n_open", "n_queued", "flags")])
 
 
@@ -205,6 +222,11 @@ class FleetDelayEpisodeArgs(ct.Structure):
     """acl_fleet_delay_episode_args_t (added within ABI 11): the episodes with
     per-link message latency."""
     _fields_ = [("base", FleetEpisodeArgs), ("lat", ct.c_void_p), ("max_lat", ct.c_int32)]
+
+
+class FleetLossyEpisodeArgs(ct.Structure):
+    """acl_fleet_lossy_episode_args_t (added within ABI 11)."""
+    _fields_ = [("delay", FleetDelayEpisodeArgs), ("link", FleetLoss)]
 
 
 FLEET_EPISODE_STATUS_DTYPE = np.dtype([(k, "<i4") for k in (
@@ -264,6 +286,11 @@ class FleetDelayTrialArgs(ct.Structure):
     """acl_fleet_delay_trial_args_t (added within ABI 11): the trials with
     per-link message latency."""
     _fields_ = [("base", FleetTrialArgs), ("lat", ct.c_void_p), ("max_lat", ct.c_int32)]
+
+
+class FleetLossyTrialArgs(ct.Structure):
+    """acl_fleet_lossy_trial_args_t (added within ABI 11)."""
+    _fields_ = [("delay", FleetDelayTrialArgs), ("link", FleetLoss)]
 
 
 HUNG_BAD_INPUT = 0x01
@@ -379,6 +406,11 @@ def lib():
     L.acl_fleet_delay_trial_batch.argtypes = [ct.POINTER(Formations),
                                               ct.POINTER(FleetDelayTrialArgs), VP]
     L.acl_fleet_delay_trial_batch.restype = ct.c_int
+    for fn, args in (("acl_fleet_lossy_auction_batch", FleetLossyArgs),
+                     ("acl_fleet_lossy_episode_batch", FleetLossyEpisodeArgs),
+                     ("acl_fleet_lossy_trial_batch", FleetLossyTrialArgs)):
+        getattr(L, fn).argtypes = [ct.POINTER(Formations), ct.POINTER(args), VP]
+        getattr(L, fn).restype = ct.c_int
     L.acl_write_assignment_log.argtypes = [ct.c_char_p, I32, VP, VP, VP, VP, VP, VP]
     L.acl_write_assignment_log.restype = ct.c_int
     L.acl_read_assignment_log.argtypes = [ct.c_char_p, ct.POINTER(I32), VP, VP, VP, VP, VP, VP]

@@ -41,6 +41,15 @@
 // per lane, and a ballot picks the entries that are due at w in this tick.
 // The latency matrix is validated and staged in LDS (n^2 bytes) before any
 // state is touched. The processing phase is the same code.
+//
+// The lossy instantiations (D and Lo; acl_fleet_lossy_auction_batch) differ
+// from the delay ones in that delivery loop only: every lane hashes the header
+// it holds (seed, receiver, sender, publication tick, iter), a second ballot
+// marks the due entries whose hash falls below the link's threshold, and the
+// serial walk sees what is left. The loss matrix is staged in LDS beside lat
+// (2 n^2 bytes more; read from global memory, a threshold cost a second round
+// trip per (receiver, sender) pair in front of the header loads). No state, no
+// atomics: the receiver's wave adds its count to n_lost once per delivery phase.
 #include "common.h"
 #include "cbaa_select_dev.h"  // step_select
 #include "fleet_dev.h"        // FleetMeta, fleet_layout, role_phys, the table helpers
@@ -91,6 +100,23 @@ struct FleetParams {
   int max_lat;
 };
 
+// The lossy instantiations' argument: FleetParams and the link's loss. A type
+// of its own, so that the other instantiations keep their kernel arguments.
+struct FleetLossParams : FleetParams {
+  const uint16_t* loss;  // [B][n][n] receiver-major
+  const uint32_t* seed;  // [B]
+  int32_t* n_lost;       // [B][n]
+};
+
+template <bool Lo>
+struct FleetKernelParams {
+  using type = FleetParams;
+};
+template <>
+struct FleetKernelParams<true> {
+  using type = FleetLossParams;
+};
+
 // What the delay instantiations stage in LDS on top of the kernel's own: every
 // vehicle's log bookkeeping, the latency matrix lat[w * n + u] and each
 // sender's slowest link. (A function-scope variable, so that the
@@ -105,6 +131,19 @@ struct FleetDelayLds {
 template <int S>
 __device__ __forceinline__ FleetDelayLds<S>& fleet_delay_lds() {
   __shared__ FleetDelayLds<S> d;
+  return d;
+}
+
+// What the lossy instantiations stage on top of that: the loss matrix
+// loss[w * n + u], beside lat. (Function scope again: the others allocate none.)
+template <int S>
+struct FleetLossLds {
+  unsigned short loss[64 * S * 64 * S];
+};
+
+template <int S>
+__device__ __forceinline__ FleetLossLds<S>& fleet_loss_lds() {
+  __shared__ FleetLossLds<S> d;
   return d;
 }
 
@@ -187,9 +226,31 @@ __device__ __forceinline__ void fleet_sub_mask(const unsigned long long* adjrow,
   sub[1] = ((unsigned long long)w3 << 32) | w2;
 }
 
-template <int S, bool D>
+// link_hash of include/aclswarm_amd.h after its first word: h0 is the state
+// that (seed, receiver, sender) alone give, the same for every bid of a link.
+__device__ __forceinline__ unsigned fleet_link_hash0(unsigned seed, int w, int u) {
+  unsigned h = (seed ^ (((unsigned)w << 16) | (unsigned)u)) * 0x9E3779B1u;
+  return h ^ (h >> 15);
+}
+
+__device__ __forceinline__ unsigned fleet_link_hash(unsigned h, int pub, int iter) {
+  h = (h ^ (unsigned)pub) * 0x9E3779B1u;
+  h ^= h >> 15;
+  h = (h ^ (unsigned)iter) * 0x9E3779B1u;
+  h ^= h >> 15;
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h *= 0xC2B2AE35u;
+  return h ^ (h >> 16);
+}
+
+// Lo (with D only; acl_fleet_lossy_auction_batch): seeded per-link message
+// loss, a decision in the delay delivery loop and nothing else.
+template <int S, bool D, bool Lo = false>
 __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
-    fleet_auction_kernel(const FleetParams P) {
+    fleet_auction_kernel(const typename FleetKernelParams<Lo>::type P) {
+  static_assert(D || !Lo, "loss is a decision of the delay delivery loop");
   constexpr int W = FleetWaves<S>::value;
   __shared__ FleetMeta meta_s[kFleetMaxN];
   __shared__ unsigned long long sub_s[kFleetMaxN][2];
@@ -221,6 +282,7 @@ __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
   }
   // ---- delay: the swarm's latency matrix, checked before any state is touched ----
   FleetDelayLds<S>& dl = fleet_delay_lds<S>();  // (unused, so not allocated, without D)
+  FleetLossLds<S>& ll = fleet_loss_lds<S>();    // (the same without Lo)
   const int R = D ? fleet_log_len(P.max_lat) : 0;  // a vehicle's log, in entries
   if constexpr (D) {
     const uint8_t* latb = P.lat + (size_t)b * n * n;
@@ -234,6 +296,7 @@ __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
       else if (l < 1 || l > P.max_lat) bad = true;
       else atomicMax(&dl.reach[u], l);
       dl.lat[k] = (unsigned char)l;
+      if constexpr (Lo) ll.loss[k] = P.loss[(size_t)b * n * n + k];
     }
     if (__syncthreads_or(bad)) {  // block-uniform: the swarm is untouched
       if (tid == 0) {
@@ -263,6 +326,8 @@ __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
   const double* pf = P.p + (size_t)f * n * 3;
   const int max_iter = P.max_iter > 0 ? P.max_iter : 2 * n;
   const int tick0 = hdr[0];
+  unsigned seed = 0u;  // (Lo) this swarm's
+  if constexpr (Lo) seed = P.seed[b];
   double* st = stage_s[wv];
   unsigned short* inv = inv_s[wv];
 
@@ -437,6 +502,7 @@ __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
     for (int w = wv; w < n; w += W) {
       int qh = meta_s[w].qhead, ql = meta_s[w].qlen;
       bool dropped = false;
+      int nlost = 0;  // (Lo) due at w in this phase and lost
       int* qw = queue_g + (size_t)w * cap * ew;
       for (int hw = 0; hw < NW; ++hw) {
         unsigned long long mm = uniform_u64(sub_s[w][hw] & pend_s[(t + 1) & 1][hw]);
@@ -451,6 +517,13 @@ __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
             const int due = tick0 + t - __builtin_amdgcn_readfirstlane((int)dl.lat[w * n + u]);
             const int* uh = loghdr_g + (size_t)u * R * 2;
             const float* ut = logtab_g + (size_t)u * R * tw;
+            // (Lo) the link's threshold, staged in LDS beside lat, and the
+            // hash after its first word: both the same for every bid of the link
+            unsigned thr = 0u, h0 = 0u;
+            if constexpr (Lo) {
+              thr = (unsigned)__builtin_amdgcn_readfirstlane((int)ll.loss[w * n + u]);
+              h0 = fleet_link_hash0(seed, w, u);
+            }
             for (int base = 0; base < cnt; base += 64) {
               const int k = base + lane;
               int hs = first + k;
@@ -460,7 +533,19 @@ __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
                 hp = uh[2 * hs];
                 hi = uh[2 * hs + 1];
               }
-              unsigned long long dm = __ballot(k < cnt && hp == due);
+              const bool due_k = k < cnt && hp == due;
+              unsigned long long dm = __ballot(due_k);
+              if constexpr (Lo) {
+                // every lane hashes its own header; the walk below sees only
+                // what is left, so the multiplies stay off the serial path
+                if (thr != 0u && dm != 0ull) {  // wave-uniform
+                  const bool lost =
+                      thr == 0xFFFFu || (fleet_link_hash(h0, hp, hi) >> 16) < thr;
+                  const unsigned long long lm = __ballot(lost) & dm;
+                  nlost += __builtin_popcountll(lm);
+                  dm &= ~lm;
+                }
+              }
               while (dm) {
                 const int kk = __builtin_ctzll(dm);
                 dm &= dm - 1;
@@ -515,6 +600,9 @@ __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
         if (dropped) {
           P.vflags[vb + w] |= ACL_FLEET_V_OVERFLOW;
           ovf_s = 1;
+        }
+        if constexpr (Lo) {
+          if (nlost) P.n_lost[vb + w] += nlost;  // receiver-owned: one writer
         }
       }
     }
@@ -863,15 +951,15 @@ static FleetParams fleet_params(const acl_formations_t* F, const acl_fleet_aucti
   return P;
 }
 
-template <bool D>
-static acl_status_t fleet_launch(const FleetParams& P, void* stream) {
+template <bool D, bool Lo = false>
+static acl_status_t fleet_launch(const typename FleetKernelParams<Lo>::type& P, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (P.n <= 64)
-    hipLaunchKernelGGL((fleet_auction_kernel<1, D>), dim3(P.B), dim3(64 * FleetWaves<1>::value), 0,
-                       s, P);
+    hipLaunchKernelGGL((fleet_auction_kernel<1, D, Lo>), dim3(P.B),
+                       dim3(64 * FleetWaves<1>::value), 0, s, P);
   else
-    hipLaunchKernelGGL((fleet_auction_kernel<2, D>), dim3(P.B), dim3(64 * FleetWaves<2>::value), 0,
-                       s, P);
+    hipLaunchKernelGGL((fleet_auction_kernel<2, D, Lo>), dim3(P.B),
+                       dim3(64 * FleetWaves<2>::value), 0, s, P);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return acl__set_error(hipGetErrorString(e));
   return ACL_OK;
@@ -891,12 +979,13 @@ extern "C" acl_status_t acl_fleet_auction_batch(const acl_formations_t* F,
   return fleet_launch<false>(fleet_params(F, a), stream);
 }
 
-extern "C" acl_status_t acl_fleet_delay_auction_batch(const acl_formations_t* F,
-                                                      const acl_fleet_delay_args_t* d,
-                                                      void* stream) {
-  using namespace acl_amd;
-  static const char entry[] = "acl_fleet_delay_auction_batch";
-  if (!d) return fleet_error(entry, "null argument");
+namespace acl_amd {
+
+// acl_fleet_delay_auction_batch, and with link acl_fleet_lossy_auction_batch:
+// the same checks in the same order, then link's own.
+static acl_status_t fleet_delay_run(const char* entry, const acl_formations_t* F,
+                                    const acl_fleet_delay_args_t* d,
+                                    const acl_fleet_loss_t* link, void* stream) {
   const acl_fleet_auction_args_t* a = &d->base;
   bool launch;
   const acl_status_t st = fleet_check(entry, F, a, &launch);
@@ -905,10 +994,37 @@ extern "C" acl_status_t acl_fleet_delay_auction_batch(const acl_formations_t* F,
     return fleet_error(entry, "max_lat out of range [1, 64]");
   if (!launch) return ACL_OK;
   if (!d->lat) return fleet_error(entry, "lat is NULL");
+  if (link && !link->loss) return fleet_error(entry, "loss is NULL");
+  if (link && !link->seed) return fleet_error(entry, "seed is NULL");
+  if (link && !link->n_lost) return fleet_error(entry, "n_lost is NULL");
   if (a->workspace_bytes < acl_fleet_delay_workspace_bytes(F->n, a->B, a->queue_cap, d->max_lat))
     return fleet_error(entry, "workspace_bytes is too small (acl_fleet_delay_workspace_bytes)");
   FleetParams P = fleet_params(F, a);
   P.lat = d->lat;
   P.max_lat = d->max_lat;
-  return fleet_launch<true>(P, stream);
+  if (!link) return fleet_launch<true>(P, stream);
+  FleetLossParams PL;
+  static_cast<FleetParams&>(PL) = P;
+  PL.loss = link->loss;
+  PL.seed = link->seed;
+  PL.n_lost = link->n_lost;
+  return fleet_launch<true, true>(PL, stream);
+}
+
+}  // namespace acl_amd
+
+extern "C" acl_status_t acl_fleet_delay_auction_batch(const acl_formations_t* F,
+                                                      const acl_fleet_delay_args_t* d,
+                                                      void* stream) {
+  static const char entry[] = "acl_fleet_delay_auction_batch";
+  if (!d) return acl_amd::fleet_error(entry, "null argument");
+  return acl_amd::fleet_delay_run(entry, F, d, nullptr, stream);
+}
+
+extern "C" acl_status_t acl_fleet_lossy_auction_batch(const acl_formations_t* F,
+                                                      const acl_fleet_lossy_args_t* l,
+                                                      void* stream) {
+  static const char entry[] = "acl_fleet_lossy_auction_batch";
+  if (!l) return acl_amd::fleet_error(entry, "null argument");
+  return acl_amd::fleet_delay_run(entry, F, &l->delay, &l->link, stream);
 }

@@ -300,12 +300,13 @@ extern "C" size_t acl_fleet_delay_episode_workspace_bytes(int32_t n, int32_t B, 
 
 namespace {
 
-// The host loop of both entries. delay: the ticks are
+// The host loop of the three entries. delay: the ticks are
 // acl_fleet_delay_auction_batch's under (lat, max_lat) on the delay workspace
 // layout; otherwise acl_fleet_auction_batch's, and lat / max_lat are unused.
+// link (with delay): the ticks are acl_fleet_lossy_auction_batch's under it.
 acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
                      const acl_fleet_episode_args_t* a, const uint8_t* lat, int max_lat,
-                     void* stream) {
+                     const acl_fleet_loss_t* link, void* stream) {
   using namespace acl_amd;
   static char msg[200];
   auto fail = [&](const char* what) {
@@ -335,6 +336,9 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
       !a->fst || !a->workspace)
     return fail("required pointer is NULL");
   if (delay && !lat) return fail("lat is NULL");
+  if (link && !link->loss) return fail("loss is NULL");
+  if (link && !link->seed) return fail("seed is NULL");
+  if (link && !link->n_lost) return fail("n_lost is NULL");
   const FepLayout W = fep_layout(n, B, a->queue_cap, max_lat);
   if (a->workspace_bytes < W.total)
     return fail(delay ? "workspace_bytes is too small (acl_fleet_delay_episode_workspace_bytes)"
@@ -364,7 +368,9 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
 
   // the ticks: the fleet kernel on the episode's state; its vflags are the
   // step's own (A.vf, cleared by the hand-off), the caller's stay sticky
-  acl_fleet_delay_args_t fd = {};
+  acl_fleet_lossy_args_t fl = {};
+  if (link) fl.link = *link;
+  acl_fleet_delay_args_t& fd = fl.delay;
   fd.lat = lat; fd.max_lat = max_lat;
   acl_fleet_auction_args_t& fa = fd.base;
   fa.B = B; fa.ticks = a->ticks_per_step; fa.max_iter = a->max_iter; fa.queue_cap = a->queue_cap;
@@ -416,8 +422,9 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
         return acl__set_error("fleet_cmd_kernel launch failed");
     }
     fa.cmd = auction ? cmd : nullptr;
-    acl_status_t r = delay ? acl_fleet_delay_auction_batch(F, &fd, stream)
-                           : acl_fleet_auction_batch(F, &fa, stream);
+    acl_status_t r = link    ? acl_fleet_lossy_auction_batch(F, &fl, stream)
+                     : delay ? acl_fleet_delay_auction_batch(F, &fd, stream)
+                             : acl_fleet_auction_batch(F, &fa, stream);
     if (r != ACL_OK) return r;
     hipLaunchKernelGGL(fleet_handoff_kernel<false>, dim3(B), dim3(kFepBlock), 0, s, A);
     if (hipGetLastError() != hipSuccess)
@@ -437,12 +444,22 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
 
 extern "C" acl_status_t acl_fleet_episode_batch(const acl_formations_t* F,
                                                 const acl_fleet_episode_args_t* a, void* stream) {
-  return fep_run("acl_fleet_episode_batch", false, F, a, nullptr, 0, stream);
+  return fep_run("acl_fleet_episode_batch", false, F, a, nullptr, 0, nullptr, stream);
 }
 
 extern "C" acl_status_t acl_fleet_delay_episode_batch(const acl_formations_t* F,
                                                       const acl_fleet_delay_episode_args_t* d,
                                                       void* stream) {
   if (!d) return acl__set_error("acl_fleet_delay_episode_batch: null argument");
-  return fep_run("acl_fleet_delay_episode_batch", true, F, &d->base, d->lat, d->max_lat, stream);
+  return fep_run("acl_fleet_delay_episode_batch", true, F, &d->base, d->lat, d->max_lat, nullptr,
+                 stream);
+}
+
+extern "C" acl_status_t acl_fleet_lossy_episode_batch(const acl_formations_t* F,
+                                                      const acl_fleet_lossy_episode_args_t* l,
+                                                      void* stream) {
+  if (!l) return acl__set_error("acl_fleet_lossy_episode_batch: null argument");
+  const acl_fleet_delay_episode_args_t* d = &l->delay;
+  return fep_run("acl_fleet_lossy_episode_batch", true, F, &d->base, d->lat, d->max_lat, &l->link,
+                 stream);
 }

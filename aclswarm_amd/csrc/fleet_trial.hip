@@ -541,8 +541,9 @@ namespace {
 struct FtrDelay {
   const uint8_t* lat;
   int max_lat, R;
+  const acl_fleet_loss_t* link;  // acl_fleet_lossy_trial_batch only
 };
-constexpr FtrDelay kNoDelay = {nullptr, 0, 0};
+constexpr FtrDelay kNoDelay = {nullptr, 0, 0, nullptr};
 
 // (after ftr_check; before anything else reads max_lat)
 acl_status_t ftr_delay(const acl_fleet_delay_trial_args_t* d, const char* who, FtrDelay* out) {
@@ -551,7 +552,7 @@ acl_status_t ftr_delay(const acl_fleet_delay_trial_args_t* d, const char* who, F
     snprintf(msg, sizeof(msg), "%s: max_lat out of range [1, 64]", who);
     return acl__set_error(msg);
   }
-  *out = FtrDelay{d->lat, d->max_lat, acl_amd::fleet_log_len(d->max_lat)};
+  *out = FtrDelay{d->lat, d->max_lat, acl_amd::fleet_log_len(d->max_lat), nullptr};
   return ACL_OK;
 }
 
@@ -596,6 +597,9 @@ acl_status_t ftr_pointers(const acl_fleet_trial_args_t* a, int n, const char* wh
       !a->workspace)
     return fail("required pointer is NULL");
   if (dl.R && !dl.lat) return fail("lat is NULL");
+  if (dl.link && !dl.link->loss) return fail("loss is NULL");
+  if (dl.link && !dl.link->seed) return fail("seed is NULL");
+  if (dl.link && !dl.link->n_lost) return fail("n_lost is NULL");
   if (a->workspace_bytes < acl_amd::ftr_layout(n, a->B, a->queue_cap, dl.R).total)
     return fail(dl.R ? "workspace_bytes is too small (acl_fleet_delay_trial_workspace_bytes)"
                      : "workspace_bytes is too small (acl_fleet_trial_workspace_bytes)");
@@ -680,9 +684,10 @@ acl_status_t ftr_init(const char* who, const acl_fleet_trial_args_t* a, int n, c
   return ACL_OK;
 }
 
-// The host loop of acl_fleet_trial_batch and acl_fleet_delay_trial_batch (after
-// ftr_check). With dl.R the ticks are acl_fleet_delay_auction_batch's under
-// (dl.lat, dl.max_lat) on the delay workspace layout.
+// The host loop of acl_fleet_trial_batch, acl_fleet_delay_trial_batch and
+// acl_fleet_lossy_trial_batch (after ftr_check). With dl.R the ticks are
+// acl_fleet_delay_auction_batch's under (dl.lat, dl.max_lat) on the delay
+// workspace layout; with dl.link acl_fleet_lossy_auction_batch's under it.
 acl_status_t ftr_run(const char* who, const acl_formations_t* F, const acl_fleet_trial_args_t* a,
                      const FtrDelay& dl, void* stream) {
   using namespace acl_amd;
@@ -707,7 +712,9 @@ acl_status_t ftr_run(const char* who, const acl_formations_t* F, const acl_fleet
 
   // the ticks: the fleet kernel on the trial's state; its vflags are the
   // step's own (A.vf, cleared by the hand-off), the caller's stay sticky
-  acl_fleet_delay_args_t fd = {};
+  acl_fleet_lossy_args_t fl = {};
+  if (dl.link) fl.link = *dl.link;
+  acl_fleet_delay_args_t& fd = fl.delay;
   fd.lat = dl.lat; fd.max_lat = dl.max_lat;
   acl_fleet_auction_args_t& fa = fd.base;
   fa.B = B; fa.ticks = a->ticks_per_step; fa.max_iter = a->max_iter; fa.queue_cap = a->queue_cap;
@@ -750,8 +757,9 @@ acl_status_t ftr_run(const char* who, const acl_formations_t* F, const acl_fleet
       hipLaunchKernelGGL(fleet_trial_pre_kernel<false>, dim3(B), dim3(kFtrBlock), 0, s, A);
     if (hipGetLastError() != hipSuccess)
       return acl__set_error("fleet_trial_pre_kernel launch failed");
-    r = delay ? acl_fleet_delay_auction_batch(F, &fd, stream)
-              : acl_fleet_auction_batch(F, &fa, stream);
+    r = dl.link ? acl_fleet_lossy_auction_batch(F, &fl, stream)
+        : delay ? acl_fleet_delay_auction_batch(F, &fd, stream)
+                : acl_fleet_auction_batch(F, &fa, stream);
     if (r != ACL_OK) return r;
     hipLaunchKernelGGL(fleet_trial_handoff_kernel<false>, dim3(B), dim3(kFtrBlock), 0, s, A);
     if (hipGetLastError() != hipSuccess)
@@ -805,5 +813,19 @@ extern "C" acl_status_t acl_fleet_delay_trial_batch(const acl_formations_t* F,
   if (r != ACL_OK) return r;
   FtrDelay dl;
   r = ftr_delay(d, who, &dl);
+  return r != ACL_OK ? r : ftr_run(who, F, &d->base, dl, stream);
+}
+
+extern "C" acl_status_t acl_fleet_lossy_trial_batch(const acl_formations_t* F,
+                                                    const acl_fleet_lossy_trial_args_t* l,
+                                                    void* stream) {
+  static const char who[] = "acl_fleet_lossy_trial_batch";
+  if (!F || !l) return acl__set_error("acl_fleet_lossy_trial_batch: null argument");
+  const acl_fleet_delay_trial_args_t* d = &l->delay;
+  acl_status_t r = ftr_check(&d->base, F->n, who);
+  if (r != ACL_OK) return r;
+  FtrDelay dl;
+  r = ftr_delay(d, who, &dl);
+  dl.link = &l->link;
   return r != ACL_OK ? r : ftr_run(who, F, &d->base, dl, stream);
 }

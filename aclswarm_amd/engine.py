@@ -445,7 +445,105 @@ def vehicle_start(table, fidx, vehid, q, Pt, qidx=None, want_bid=True, stream=No
     return out
 
 
-class FleetAuction:
+class _LossyLinks:
+    """loss / loss_seed of FleetAuction, FleetEpisode and FleetTrial: seeded
+    per-link message loss (the acl_fleet_lossy_* entries; include/aclswarm_amd.h
+    states the rule). loss: an int in 0..65535 for every link (0: never lost,
+    65535: dead, k: probability k / 65536), or a contiguous uint16 / int16
+    (uint16 bits) tensor [B][n][n], receiver-major, on the table's device; it
+    is copied. loss_seed: an int in 0..2^32 - 1 (swarm b gets seed + b mod
+    2^32), or an int32 / uint32 tensor [B]; default 0. Both are attributes the
+    caller may replace between runs, with the same checks; loss = None goes
+    back to the entry with latency alone on the same workspace. n_lost
+    [B][n] i32 counts the bids lost per receiver over the object's life."""
+
+    _loss = None
+    _loss_seed = None
+    n_lost = None
+
+    @staticmethod
+    def _is_int(x):
+        return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+
+    @classmethod
+    def _loss_latency(cls, what, loss, loss_seed, latency):
+        """The latency a lossy object runs under: the caller's, or 1 on every
+        link (loss lives in the delay entries' delivery)."""
+        if loss is None:
+            if loss_seed is not None:
+                raise ValueError(f"{what}: loss_seed is given without loss")
+            return latency
+        return 1 if latency is None else latency
+
+    @classmethod
+    def _loss_tensor(cls, what, loss, B, n, dev):
+        if cls._is_int(loss):
+            if not 0 <= int(loss) <= 0xFFFF:
+                raise ValueError(f"{what}: loss = {loss} out of range [0, 65535]")
+            bits = int(loss) - 0x10000 if int(loss) >= 0x8000 else int(loss)
+            return torch.full((B, n, n), bits, dtype=torch.int16, device=dev)
+        dts = tuple(d for d in (getattr(torch, "uint16", None), torch.int16) if d is not None)
+        FleetAuction._check(what, {"loss": (loss, dts, (B, n, n))}, dev)
+        return loss.clone()
+
+    @classmethod
+    def _seed_tensor(cls, what, seed, B, dev):
+        if cls._is_int(seed):
+            if not 0 <= int(seed) <= 0xFFFFFFFF:
+                raise ValueError(f"{what}: loss_seed = {seed} out of range [0, 2^32 - 1]")
+            x = (torch.arange(B, dtype=torch.int64) + int(seed)) & 0xFFFFFFFF
+            x = (x + 0x80000000) % 0x100000000 - 0x80000000  # the uint32 bits as int32
+            return x.to(torch.int32).to(dev)
+        dts = tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)
+        FleetAuction._check(what, {"loss_seed": (seed, dts, (B,))}, dev)
+        return seed.clone()
+
+    def _loss_setup(self, what, loss, loss_seed, B, n, dev):
+        """(constructor) the checked copies, before anything is allocated or run."""
+        if loss is None:
+            return
+        self._loss = self._loss_tensor(what, loss, B, n, dev)
+        self._loss_seed = self._seed_tensor(what, 0 if loss_seed is None else loss_seed, B, dev)
+        self.n_lost = torch.zeros((B, n), dtype=torch.int32, device=dev)
+
+    @property
+    def loss(self):
+        return self._loss
+
+    @loss.setter
+    def loss(self, loss):
+        what = type(self).__name__
+        if loss is None:
+            self._loss = None
+            return
+        if self.latency is None:
+            raise ValueError(f"{what}: loss needs the workspace of the entries with latency; "
+                             "construct the object with loss or latency")
+        self._loss = self._loss_tensor(what, loss, self.B, self.n, self.device)
+        if self._loss_seed is None:
+            self._loss_seed = self._seed_tensor(what, 0, self.B, self.device)
+        if self.n_lost is None:
+            self.n_lost = torch.zeros((self.B, self.n), dtype=torch.int32, device=self.device)
+
+    @property
+    def loss_seed(self):
+        return self._loss_seed
+
+    @loss_seed.setter
+    def loss_seed(self, seed):
+        what = type(self).__name__
+        if self._loss is None:
+            raise ValueError(f"{what}: loss_seed is given without loss")
+        self._loss_seed = self._seed_tensor(what, seed, self.B, self.device)
+
+    def _link(self, link):
+        """Fills an acl_fleet_loss_t."""
+        link.loss = self._loss.data_ptr()
+        link.seed = self._loss_seed.data_ptr()
+        link.n_lost = self.n_lost.data_ptr()
+
+
+class FleetAuction(_LossyLinks):
     """acl_fleet_auction_batch (added within ABI 11): the message-level CBAA of
     B swarms of n vehicles -- every vehicle an Auctioneer of the reference
     with its receive queue and START / current / next buckets -- advanced tick
@@ -470,10 +568,16 @@ class FleetAuction:
     (<= 64) sizes the publication logs and defaults to the largest entry
     (reading it synchronises once, in the constructor). The latencies are
     fixed for the object's life. Raises ValueError on a malformed argument
-    before anything runs."""
+    before anything runs.
+
+    loss not None: the fleet runs acl_fleet_lossy_auction_batch, where a bid
+    that is due on link (u -> w) is lost with probability loss[b][w][u] /
+    65536 by a hash of (loss_seed[b], w, u, publication tick, iter): loss and
+    loss_seed as _LossyLinks takes them. With latency None every link takes 1
+    tick, on the delay entry's workspace. The object owns n_lost."""
 
     def __init__(self, table, fidx, Pt=None, queue_cap=None, max_iter=0, latency=None,
-                 max_latency=None):
+                 max_latency=None, loss=None, loss_seed=None):
         n = table.n
         if n < 1 or n > L.FLEET_MAX_N:
             raise ValueError(f"FleetAuction: n = {n} out of range [1, {L.FLEET_MAX_N}]")
@@ -495,7 +599,9 @@ class FleetAuction:
             raise ValueError(f"FleetAuction: max_iter = {max_iter} < 0")
         self.table, self.fidx, self.n, self.B, self.device = table, fidx, n, B, dev
         self.queue_cap, self.max_iter = int(queue_cap), int(max_iter)
+        latency = self._loss_latency("FleetAuction", loss, loss_seed, latency)
         self.latency, self.max_latency = self._latency(latency, max_latency, B, n, dev)
+        self._loss_setup("FleetAuction", loss, loss_seed, B, n, dev)
         if Pt is None:
             Pt = torch.arange(n, dtype=torch.int16, device=dev).repeat(B, n, 1)
         self.Pt = Pt.clone().contiguous()
@@ -587,7 +693,8 @@ class FleetAuction:
         if history:
             hist = {"biditer": torch.empty((ticks, B, n), dtype=torch.int32, device=dev),
                     "open": torch.empty((ticks, B, n), dtype=torch.uint8, device=dev)}
-        d = L.FleetDelayArgs()
+        lo = L.FleetLossyArgs()
+        d = lo.delay
         a = d.base if self.latency is not None else L.FleetAuctionArgs()
         a.B, a.ticks, a.max_iter, a.queue_cap = B, ticks, self.max_iter, self.queue_cap
         a.fidx = self.fidx.data_ptr()
@@ -608,6 +715,12 @@ class FleetAuction:
             stream = torch.cuda.current_stream(dev).cuda_stream
         if self.latency is not None:
             d.lat, d.max_lat = self.latency.data_ptr(), self.max_latency
+        if self._loss is not None:
+            self._link(lo.link)
+            L.check(L.lib().acl_fleet_lossy_auction_batch(ct.byref(F), ct.byref(lo),
+                                                          ct.c_void_p(stream)),
+                    "acl_fleet_lossy_auction_batch")
+        elif self.latency is not None:
             L.check(L.lib().acl_fleet_delay_auction_batch(ct.byref(F), ct.byref(d),
                                                           ct.c_void_p(stream)),
                     "acl_fleet_delay_auction_batch")
@@ -765,7 +878,7 @@ class Episode:
         return arr.view(L.EPISODE_STATUS_DTYPE).reshape(-1)
 
 
-class FleetEpisode:
+class FleetEpisode(_LossyLinks):
     """Closed-loop episodes on the message-level auction
     (acl_fleet_episode_batch, added within ABI 11): B swarms of n <= 128
     vehicles, every vehicle its own Auctioneer (FleetAuction's model) with its
@@ -788,14 +901,19 @@ class FleetEpisode:
     acl_fleet_delay_episode_batch: the steps' ticks are those of the fleet
     auction with per-link latency, with latency and max_latency exactly as
     FleetAuction takes them (an int, or a uint8 tensor [B][n][n],
-    receiver-major; fixed for the object's life)."""
+    receiver-major; fixed for the object's life).
+
+    loss not None: acl_fleet_lossy_episode_batch, with loss and loss_seed
+    exactly as FleetAuction takes them (latency None: 1 tick on every link);
+    the object owns n_lost, which accumulates across steps and runs."""
 
     FLEET_KEYS = ("Pt", "open", "invalid", "just_received", "biditer", "price", "who", "Rt",
                   "final_price", "final_who", "done_tick", "vflags", "n_thrown", "n_tally",
                   "queue_len")
 
     def __init__(self, table, fidx, q, vel, Pt=None, params=None, cntrl=None, safety=None,
-                 queue_cap=None, max_iter=0, ticks_per_step=10, latency=None, max_latency=None):
+                 queue_cap=None, max_iter=0, ticks_per_step=10, latency=None, max_latency=None,
+                 loss=None, loss_seed=None):
         n = table.n
         if n < 1 or n > L.FLEET_MAX_N:
             raise ValueError(f"FleetEpisode: n = {n} out of range [1, {L.FLEET_MAX_N}]")
@@ -821,7 +939,9 @@ class FleetEpisode:
             want["Pt"] = (Pt, torch.int16, (B, n, n))
         _check_state("FleetEpisode", table, want)
         dev = q.device
+        latency = self._loss_latency("FleetEpisode", loss, loss_seed, latency)
         self.latency, self.max_latency = FleetAuction._latency(latency, max_latency, B, n, dev)
+        self._loss_setup("FleetEpisode", loss, loss_seed, B, n, dev)
         if Pt is None:
             Pt = torch.arange(n, dtype=torch.int16, device=dev).repeat(B, n, 1)
         elif not torch.equal(torch.sort(Pt.to(torch.int32) & 0xFFFF, dim=2).values,
@@ -898,7 +1018,8 @@ class FleetEpisode:
                 "P": torch.zeros((steps, B, n), dtype=torch.int16, device=dev),
                 "vflags": torch.zeros((steps, B, n), dtype=torch.int32, device=dev),
             }
-        d = L.FleetDelayEpisodeArgs()
+        lo = L.FleetLossyEpisodeArgs()
+        d = lo.delay
         a = d.base if self.latency is not None else L.FleetEpisodeArgs()
         a.B, a.step0, a.steps, a.ticks_per_step = B, self.step, steps, self.ticks_per_step
         a.max_iter, a.queue_cap = self.max_iter, self.queue_cap
@@ -917,6 +1038,12 @@ class FleetEpisode:
             stream = torch.cuda.current_stream(dev).cuda_stream
         if self.latency is not None:
             d.lat, d.max_lat = self.latency.data_ptr(), self.max_latency
+        if self._loss is not None:
+            self._link(lo.link)
+            L.check(L.lib().acl_fleet_lossy_episode_batch(ct.byref(F), ct.byref(lo),
+                                                          ct.c_void_p(stream)),
+                    "acl_fleet_lossy_episode_batch")
+        elif self.latency is not None:
             L.check(L.lib().acl_fleet_delay_episode_batch(ct.byref(F), ct.byref(d),
                                                           ct.c_void_p(stream)),
                     "acl_fleet_delay_episode_batch")
@@ -1045,7 +1172,7 @@ class Trial:
                 "done_step": st["done_step"].copy()}
 
 
-class FleetTrial:
+class FleetTrial(_LossyLinks):
     """Monte-Carlo trials on the message-level auction (acl_fleet_trial_batch,
     added within ABI 11): Trial's supervisor, formation sequence and
     controller starts over FleetAuction's per-vehicle auctioneers, B swarms of
@@ -1064,14 +1191,20 @@ class FleetTrial:
     acl_fleet_delay_trial_init / acl_fleet_delay_trial_batch: the steps' ticks
     are those of the fleet auction with per-link latency, with latency and
     max_latency exactly as FleetAuction takes them (an int, or a uint8 tensor
-    [B][n][n], receiver-major; fixed for the object's life)."""
+    [B][n][n], receiver-major; fixed for the object's life).
+
+    loss not None: acl_fleet_lossy_trial_batch (the init is the delay
+    entry's), with loss and loss_seed exactly as FleetAuction takes them
+    (latency None: 1 tick on every link); the object owns n_lost, which
+    accumulates across steps and runs. Only the vehicles' bids are lossy."""
 
     TRIAL_KEYS = ("fseq", "fidx", "q", "vel", "P", "ts", "ctl_on", "ring_u", "ring_ca", "posf",
                   "dist", "t_conv", "t_avoid", "n_assign")
     FLEET_KEYS = FleetEpisode.FLEET_KEYS + ("adopt_step", "fst")
 
     def __init__(self, table, fseq, q, vel, params=None, cntrl=None, safety=None, queue_cap=None,
-                 max_iter=0, ticks_per_step=10, latency=None, max_latency=None):
+                 max_iter=0, ticks_per_step=10, latency=None, max_latency=None, loss=None,
+                 loss_seed=None):
         n = table.n
         if n < 1 or n > L.FLEET_MAX_N:
             raise ValueError(f"FleetTrial: n = {n} out of range [1, {L.FLEET_MAX_N}]")
@@ -1095,7 +1228,9 @@ class FleetTrial:
                                            "vel": (vel, torch.float64, (B, n, 3)),
                                            "fseq": (fseq, torch.int32, (B, None))})
         dev = q.device
+        latency = self._loss_latency("FleetTrial", loss, loss_seed, latency)
         self.latency, self.max_latency = FleetAuction._latency(latency, max_latency, B, n, dev)
+        self._loss_setup("FleetTrial", loss, loss_seed, B, n, dev)
         self.table, self.n, self.B, self.device = table, n, B, dev
         self.K = K = int(fseq.shape[1])
         self.queue_cap, self.max_iter = int(queue_cap), int(max_iter)
@@ -1142,7 +1277,7 @@ class FleetTrial:
         self.fst = e((B, L.FLEET_EPISODE_STATUS_DTYPE.itemsize), torch.uint8)
         self.ws = e((self.workspace_bytes(),), torch.uint8)
         self.step = 0
-        a = self._args(0)
+        a = self._args(0, lossy=False)  # (the init is the delay entry's)
         stream = ct.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         if self.latency is not None:
             L.check(L.lib().acl_fleet_delay_trial_init(ct.byref(a), n, stream),
@@ -1156,10 +1291,13 @@ class FleetTrial:
                 self.n, self.B, self.queue_cap, self.max_latency))
         return int(L.lib().acl_fleet_trial_workspace_bytes(self.n, self.B, self.queue_cap))
 
-    def _args(self, steps, hist=None):
-        """The entry's argument struct: FleetTrialArgs, or with latency the
-        FleetDelayTrialArgs around it."""
-        d = L.FleetDelayTrialArgs() if self.latency is not None else None
+    def _args(self, steps, hist=None, lossy=True):
+        """The entry's argument struct: FleetTrialArgs, with latency the
+        FleetDelayTrialArgs around it, with loss (and lossy) the
+        FleetLossyTrialArgs around that."""
+        lo = L.FleetLossyTrialArgs() if lossy and self._loss is not None else None
+        d = lo.delay if lo is not None else \
+            L.FleetDelayTrialArgs() if self.latency is not None else None
         a = d.base if d is not None else L.FleetTrialArgs()
         a.B, a.K, a.step0, a.steps = self.B, self.K, self.step, steps
         a.ticks_per_step, a.max_iter, a.queue_cap = self.ticks_per_step, self.max_iter, \
@@ -1175,6 +1313,9 @@ class FleetTrial:
         a.cntrl, a.safety, a.tp = self.cntrl, self.safety, self.tp
         if d is not None:
             d.lat, d.max_lat = self.latency.data_ptr(), self.max_latency
+            if lo is not None:
+                self._link(lo.link)
+                return lo
             return d
         return a
 
@@ -1202,7 +1343,11 @@ class FleetTrial:
         F = self.table.struct()
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
-        if self.latency is not None:
+        if self._loss is not None:
+            L.check(L.lib().acl_fleet_lossy_trial_batch(ct.byref(F), ct.byref(a),
+                                                        ct.c_void_p(stream)),
+                    "acl_fleet_lossy_trial_batch")
+        elif self.latency is not None:
             L.check(L.lib().acl_fleet_delay_trial_batch(ct.byref(F), ct.byref(a),
                                                         ct.c_void_p(stream)),
                     "acl_fleet_delay_trial_batch")

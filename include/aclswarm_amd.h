@@ -726,10 +726,10 @@ acl_status_t acl_fleet_auction_batch(const acl_formations_t* formations,
  * workspace_bytes too small. n in [1, 128]. Stream-ordered, never
  * synchronises.
  *
- * Not modelled: latencies that change over time and message loss. The closed
- * loops on this entry are acl_fleet_delay_episode_batch and
- * acl_fleet_delay_trial_batch (acl_fleet_episode_batch / acl_fleet_trial_batch
- * run the entry above). */
+ * Not modelled: latencies that change over time; message loss is
+ * acl_fleet_lossy_auction_batch below. The closed loops on this entry are
+ * acl_fleet_delay_episode_batch and acl_fleet_delay_trial_batch
+ * (acl_fleet_episode_batch / acl_fleet_trial_batch run the entry above). */
 typedef struct {
   acl_fleet_auction_args_t base; /* workspace: acl_fleet_delay_workspace_bytes */
   const uint8_t* lat;            /* [B][n][n] receiver-major: lat[b][w][u], ticks from u to w */
@@ -740,6 +740,76 @@ size_t acl_fleet_delay_workspace_bytes(int32_t n, int32_t B, int32_t queue_cap,
                                        int32_t max_lat);
 acl_status_t acl_fleet_delay_auction_batch(const acl_formations_t* formations,
                                            const acl_fleet_delay_args_t* args, void* stream);
+
+/* ---- the fleet auction with seeded per-link message loss (added within ABI 11)
+ * acl_fleet_delay_auction_batch with one sentence changed: everything above
+ * holds (latency, publication ticks, the order within a delivery phase, in
+ * flight, quiescence, bad latency, capacity, the workspace and the call rules)
+ * except what happens to a bid that is due. Added symbols: ACL_ABI_VERSION
+ * stays 11 (no existing struct or call changed).
+ *
+ * The rule. A bid of sender u with publication tick P and iteration `iter` is
+ * due at receiver w in the delivery phase of tick P + lat[b][w][u]. If w
+ * subscribes to u at that moment, the bid is LOST iff
+ *
+ *   loss[b][w][u] == 0xFFFF  ||  (link_hash(seed[b], w, u, P, iter) >> 16) < loss[b][w][u]
+ *
+ * and otherwise it is appended to w's queue, or dropped with the overflow
+ * flags, exactly as above. Nothing is resent: Auctioneer::processBid runs on a
+ * received bid only, so a vehicle whose neighbour's iteration-k bid is lost
+ * never completes iteration k, its own neighbours then wait for it, and the
+ * fleet stands open and quiescent until a command restarts it.
+ *
+ * loss is [B][n][n] u16, receiver-major like lat; the diagonal is ignored.
+ * 0: never lost. 0xFFFF: a dead link. Any other k: probability k / 65536.
+ * seed is [B] u32. link_hash is, in u32 arithmetic modulo 2^32,
+ *
+ *   h = seed
+ *   for word in ((w << 16) | u, (uint32)P, (uint32)iter):
+ *       h = (h ^ word) * 0x9E3779B1;  h ^= h >> 15
+ *   h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;  h *= 0xC2B2AE35;  h ^= h >> 16
+ *
+ * (sender, P, iter) names a publication uniquely -- a command's bid has iter 0,
+ * a tally's bid iter >= 1 -- so a bid's fate depends neither on how a run is
+ * split into calls nor on the order in which anything is visited.
+ *
+ * Consequences.
+ *  - A lost bid takes no queue slot and raises no overflow flag: the loss test
+ *    comes before the capacity test. A bid that is due at a receiver that does
+ *    not subscribe to its sender is not delivered and not counted as lost.
+ *  - In flight and quiescence are unchanged: a bid is in flight until the
+ *    delivery phase of tick P + reach[u] has run, lost anywhere or not.
+ *  - Loss adds no state. The workspace is the delay entry's
+ *    (acl_fleet_delay_workspace_bytes, the same layout), and a swarm may move
+ *    between acl_fleet_delay_auction_batch and this entry from call to call.
+ *    loss and seed may differ from call to call: the matrix and seed of the
+ *    call in whose delivery phase a bid is due decide that bid's fate. Each
+ *    link stays FIFO.
+ *  - n_lost[b][w] (i32, in/out) is incremented once per bid lost at receiver w;
+ *    the caller zeroes it once. A swarm flagged ACL_FLEET_BAD_INPUT runs no
+ *    tick, so its n_lost does not move.
+ *  - With loss all zero this entry equals acl_fleet_delay_auction_batch bit for
+ *    bit, for any seed: state, outputs, statuses and histories.
+ *
+ * The argument checks are those of acl_fleet_delay_auction_batch on `delay`,
+ * plus: loss, seed or n_lost NULL (B > 0). Stream-ordered, never synchronises.
+ *
+ * Not modelled: latencies that change over time, loss that depends on history
+ * (bursts), n > 128. The closed loops on this entry are
+ * acl_fleet_lossy_episode_batch and acl_fleet_lossy_trial_batch. */
+typedef struct {
+  const uint16_t* loss; /* [B][n][n] receiver-major: loss[b][w][u], threshold on link u -> w */
+  const uint32_t* seed; /* [B] */
+  int32_t* n_lost;      /* [B][n] in/out, accumulated per receiver */
+} acl_fleet_loss_t;
+
+typedef struct {
+  acl_fleet_delay_args_t delay; /* workspace: acl_fleet_delay_workspace_bytes */
+  acl_fleet_loss_t link;
+} acl_fleet_lossy_args_t;
+
+acl_status_t acl_fleet_lossy_auction_batch(const acl_formations_t* formations,
+                                           const acl_fleet_lossy_args_t* args, void* stream);
 
 /* ---- closed-loop batched episodes ---------------------
  * B swarms flown for `steps` control periods in lockstep: the discrete-time
@@ -1052,8 +1122,9 @@ acl_status_t acl_fleet_episode_batch(const acl_formations_t* formations,
  *
  * With every link at 1 tick this is acl_fleet_episode_batch step for step:
  * the same state, outputs, histories and statuses.
- * Not modelled: latencies that change over time, message loss; all model
- * limits of acl_fleet_episode_batch but "latency below one tick" remain. */
+ * Not modelled: latencies that change over time; message loss is
+ * acl_fleet_lossy_episode_batch below; all model limits of
+ * acl_fleet_episode_batch but "latency below one tick" remain. */
 typedef struct {
   acl_fleet_episode_args_t base; /* workspace: acl_fleet_delay_episode_workspace_bytes */
   const uint8_t* lat;            /* [B][n][n] receiver-major, as acl_fleet_delay_args_t */
@@ -1064,6 +1135,35 @@ size_t acl_fleet_delay_episode_workspace_bytes(int32_t n, int32_t B, int32_t que
                                                int32_t max_lat);
 acl_status_t acl_fleet_delay_episode_batch(const acl_formations_t* formations,
                                            const acl_fleet_delay_episode_args_t* args,
+                                           void* stream);
+
+/* ---- the episodes with seeded per-link message loss (added within ABI 11) --
+ * acl_fleet_lossy_episode_batch is acl_fleet_delay_episode_batch with the
+ * step's ticks those of acl_fleet_lossy_auction_batch under `link`: a due bid
+ * is lost by that entry's rule, and nothing else differs. Added symbols:
+ * ACL_ABI_VERSION stays 11 (no existing struct or call changed).
+ *
+ * The workspace is acl_fleet_delay_episode_workspace_bytes, the same layout;
+ * loss adds no state, so an episode may move between the delay entry and this
+ * one from call to call, and loss and seed may differ from call to call.
+ * n_lost accumulates across steps and calls. A swarm that the call's input
+ * check flags ACL_FLEET_BAD_INPUT runs no tick, so its n_lost does not move.
+ * An auction that stalls on a lost bid stays open and quiescent until the next
+ * auto-auction's START restarts every vehicle (the restart rules of
+ * acl_fleet_episode_batch). With loss all zero this is
+ * acl_fleet_delay_episode_batch step for step, bit for bit, for any seed.
+ *
+ * The argument checks are those of acl_fleet_delay_episode_batch on `delay`,
+ * plus: loss, seed or n_lost NULL (B > 0 and steps > 0).
+ * Not modelled: latencies that change over time, loss that depends on history
+ * (bursts), n > 128. */
+typedef struct {
+  acl_fleet_delay_episode_args_t delay; /* workspace: acl_fleet_delay_episode_workspace_bytes */
+  acl_fleet_loss_t link;
+} acl_fleet_lossy_episode_args_t;
+
+acl_status_t acl_fleet_lossy_episode_batch(const acl_formations_t* formations,
+                                           const acl_fleet_lossy_episode_args_t* args,
                                            void* stream);
 
 /* ---- batched Monte-Carlo trials (ABI 9; SURVEY §8f widening of row f1) ---
@@ -1381,10 +1481,11 @@ acl_status_t acl_fleet_trial_batch(const acl_formations_t* formations,
  * acl_fleet_trial_workspace_bytes.
  *
  * With every link at 1 tick this is acl_fleet_trial_batch step for step.
- * Not modelled: latencies that change over time, message loss, and latency on
- * the supervisor's subscription to vehicle 0 (its message still arrives in the
- * step of the adoption); all model limits of acl_fleet_trial_batch but
- * "latency below one tick" remain. */
+ * Not modelled: latencies that change over time, and latency on the
+ * supervisor's subscription to vehicle 0 (its message still arrives in the
+ * step of the adoption); message loss is acl_fleet_lossy_trial_batch below;
+ * all model limits of acl_fleet_trial_batch but "latency below one tick"
+ * remain. */
 typedef struct {
   acl_fleet_trial_args_t base; /* workspace: acl_fleet_delay_trial_workspace_bytes */
   const uint8_t* lat;          /* [B][n][n] receiver-major, as acl_fleet_delay_args_t */
@@ -1397,6 +1498,36 @@ acl_status_t acl_fleet_delay_trial_init(const acl_fleet_delay_trial_args_t* args
                                         void* stream);
 acl_status_t acl_fleet_delay_trial_batch(const acl_formations_t* formations,
                                          const acl_fleet_delay_trial_args_t* args, void* stream);
+
+/* ---- the trials with seeded per-link message loss (added within ABI 11) ----
+ * acl_fleet_lossy_trial_batch is acl_fleet_delay_trial_batch with the step's
+ * ticks those of acl_fleet_lossy_auction_batch under `link`. Added symbols:
+ * ACL_ABI_VERSION stays 11 (no existing struct or call changed).
+ *
+ * The workspace and the init are the delay entries' own
+ * (acl_fleet_delay_trial_workspace_bytes, acl_fleet_delay_trial_init on
+ * `delay`): loss adds no state, a trial may move between the delay entry and
+ * this one from call to call, and loss and seed may differ from call to call.
+ * n_lost accumulates across steps and calls (the caller zeroes it once); a
+ * swarm flagged ACL_FLEET_BAD_INPUT runs no tick, so its n_lost does not move.
+ * An auction stalled by a lost bid is restarted by the next auto-auction;
+ * if no assignment arrives within tp.assignment_timeout the supervisor ends
+ * the trial as acl_fleet_trial_batch states. With loss all zero this is
+ * acl_fleet_delay_trial_batch step for step, bit for bit, for any seed.
+ *
+ * The argument checks are those of acl_fleet_delay_trial_batch on `delay`,
+ * plus: loss, seed or n_lost NULL (B > 0 and steps > 0).
+ * Not modelled: only vehicle-to-vehicle CBAA bids are lossy -- the trial's
+ * formation changes (the operator's message reaches every vehicle) and the
+ * supervisor's subscription to vehicle 0 are not; latencies that change over
+ * time; loss that depends on history (bursts); n > 128. */
+typedef struct {
+  acl_fleet_delay_trial_args_t delay; /* workspace: acl_fleet_delay_trial_workspace_bytes */
+  acl_fleet_loss_t link;
+} acl_fleet_lossy_trial_args_t;
+
+acl_status_t acl_fleet_lossy_trial_batch(const acl_formations_t* formations,
+                                         const acl_fleet_lossy_trial_args_t* args, void* stream);
 
 /* ---- random formation groups on the device -----------
  * Replaces aclswarm_sim/nodes/generate_random_formation.py:59-80

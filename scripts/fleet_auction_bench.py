@@ -21,6 +21,16 @@ With --latency L[,L...] a third path per L is alternated with them:
           (engine.FleetAuction(latency=L)): the same auction through the
           publication logs; its final tables must equal the fleet's.
 
+With --loss K[,K...] (needs --latency) a fourth path per (L, K) is alternated
+with them:
+
+  lossy   one acl_fleet_lossy_auction_batch call with every link at L ticks and
+          loss threshold K (engine.FleetAuction(latency=L, loss=K,
+          loss_seed=1)). At K = 0 its final tables must equal the fleet's and
+          the time is the feature's overhead over the delay path; at K > 0 the
+          share of swarms that reach consensus before quiescence, ticks_run
+          and the bids lost are reported.
+
 All are timed wall-clock between synchronisations after a warm-up, the paths
 alternated in one session, and the medians reported; the paced loop's final
 tables must equal the fleet's. Writes one JSON document (--out) with the
@@ -107,7 +117,7 @@ def timed(fn, dev):
     return time.perf_counter() - t0, r
 
 
-def bench(n, B, F, reps, warmup, dev, latencies=()):
+def bench(n, B, F, reps, warmup, dev, latencies=(), losses=()):
     T, adj, fidx, q = make_case(n, B, F, 1000 + n, dev)
     d_max = int(adj.sum(axis=2).max())
     ticks = 2 * n * d_max + 8
@@ -129,13 +139,25 @@ def bench(n, B, F, reps, warmup, dev, latencies=()):
         dt, _ = timed(lambda: d.run(ticks * lat, q=q, cmd=cmd), dev)
         return dt, d
 
+    def lossy(lat, loss):
+        d = engine.FleetAuction(T, fidx, latency=lat, loss=loss, loss_seed=1)
+        d.ws = torch.zeros(d.workspace_bytes(), dtype=torch.uint8, device=dev)
+        dt, _ = timed(lambda: d.run(ticks * lat, q=q, cmd=cmd), dev)
+        return dt, d
+
     t_fleet, t_paced, t_delay, last = [], [], {lat: [] for lat in latencies}, {}
+    pairs = [(lat, k) for lat in latencies for k in losses]
+    t_lossy, last_lossy = {pk: [] for pk in pairs}, {}
     for r in range(warmup + reps):
         dt_f, f = fleet()
         for lat in latencies:
             dt_d, last[lat] = delay(lat)
             if r >= warmup:
                 t_delay[lat].append(dt_d)
+            for k in losses:
+                dt_l, last_lossy[lat, k] = lossy(lat, k)
+                if r >= warmup:
+                    t_lossy[lat, k].append(dt_l)
         dt_p, who_p = timed(paced.run, dev)
         if r >= warmup:
             t_fleet.append(dt_f)
@@ -158,7 +180,24 @@ def bench(n, B, F, reps, warmup, dev, latencies=()):
                            delay_us_per_tick=md * 1e6 / trd, delay_over_fleet=md / mf,
                            workspace_bytes=d.workspace_bytes(), tables_equal=True,
                            thrown=int(d.n_thrown.sum().item())))
-    return dict(delay=delays, n=n, B=B, formations=F, d_max=d_max, queue_cap=fa.queue_cap,
+    lossies = []
+    for lat, k in pairs:
+        d, sd = last_lossy[lat, k], last_lossy[lat, k].status()
+        assert (sd["flags"] == L.FLEET_QUIESCENT).all()
+        ml, md = statistics.median(t_lossy[lat, k]), statistics.median(t_delay[lat])
+        if k == 0:
+            assert (sd["n_open"] == 0).all() and not bool(d.n_lost.any())
+            assert bool((d.final_who == f.final_who).all()), "the lossy entry's tables differ"
+        done = sd["n_open"] == 0
+        lossies.append(dict(latency=lat, loss=k, lossy_ms=ml * 1e3,
+                            lossy_ms_all=[x * 1e3 for x in t_lossy[lat, k]],
+                            lossy_over_delay=ml / md, consensus_share=float(done.mean()),
+                            ticks_run_max=int(sd["ticks_run"].max()),
+                            ticks_run_median=float(np.median(sd["ticks_run"])),
+                            ticks_run_min=int(sd["ticks_run"].min()),
+                            lost=int(d.n_lost.sum().item()),
+                            swarms_with_a_lost_bid=int((d.n_lost.sum(dim=1) > 0).sum().item())))
+    return dict(delay=delays, lossy=lossies, n=n, B=B, formations=F, d_max=d_max, queue_cap=fa.queue_cap,
                 ticks_run_max=tr, ticks_run_min=int(st["ticks_run"].min()),
                 fleet_ms=mf * 1e3, fleet_ms_all=[x * 1e3 for x in t_fleet],
                 fleet_us_per_tick=mf * 1e6 / tr,
@@ -178,6 +217,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--latency", default="", help="uniform link latencies in ticks, "
                     "comma-separated: also time acl_fleet_delay_auction_batch at each")
+    ap.add_argument("--loss", default="", help="loss thresholds 0..65535, comma-separated: also "
+                    "time acl_fleet_lossy_auction_batch at each --latency and each of these")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fleet_auction",
                                                   "latency.json"))
     a = ap.parse_args()
@@ -186,7 +227,8 @@ def main():
     for s in a.shapes.split(","):
         n, B = (int(x) for x in s.split("x"))
         r = bench(n, B, a.formations, a.reps, a.warmup, dev,
-                  [int(x) for x in a.latency.split(",") if x])
+                  [int(x) for x in a.latency.split(",") if x],
+                  [int(x) for x in a.loss.split(",") if x])
         print(json.dumps(r), flush=True)
         res.append(r)
     doc = dict(device=torch.cuda.get_device_name(dev), reps=a.reps, warmup=a.warmup,

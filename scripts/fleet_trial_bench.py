@@ -21,6 +21,10 @@ consensus, i.e. were interrupted by a commit or cut by the trial's end.
 With --latency L[,L...] a further loop per L is alternated with them: the same
 trials on acl_fleet_delay_trial_batch with every link at L ticks
 (engine.FleetTrial(latency=L)), reported as "fleet_L<L>" with the same figures.
+With --loss K[,K...] (and --latency) also acl_fleet_lossy_trial_batch at every
+(L, K) (engine.FleetTrial(latency=L, loss=K, loss_seed=1)), reported as
+"fleet_L<L>_loss<K>" with the bids lost and the share of trials that ended
+through the supervisor's assignment timeout (TERMINATE from WAITING).
 Writes one JSON document (--out)."""
 import argparse
 import json
@@ -57,7 +61,7 @@ def fly(make, max_steps, chunk, dev):
     return time.perf_counter() - t0, steps, tr
 
 
-def bench(n, B, reps, warmup, max_steps, chunk, dev, latencies=()):
+def bench(n, B, reps, warmup, max_steps, chunk, dev, latencies=(), losses=()):
     L_side = 15.0 if n <= 20 else 40.0 * (n / 100.0) ** 0.5
     T, t_admm, admm = admm_table(n, B, L_side, 0, dev)
     gen = torch.Generator(device=dev)
@@ -70,6 +74,9 @@ def bench(n, B, reps, warmup, max_steps, chunk, dev, latencies=()):
              "sync": lambda: engine.Trial(T, fseq, q, vel)}
     for lat in latencies:
         loops[f"fleet_L{lat}"] = lambda lat=lat: engine.FleetTrial(T, fseq, q, vel, latency=lat)
+        for k in losses:
+            loops[f"fleet_L{lat}_loss{k}"] = lambda lat=lat, k=k: engine.FleetTrial(
+                T, fseq, q, vel, latency=lat, loss=k, loss_seed=1)
     times = {k: [] for k in loops}
     last = {}
     for r in range(warmup + reps):
@@ -108,6 +115,14 @@ def bench(n, B, reps, warmup, max_steps, chunk, dev, latencies=()):
         out[f"fleet_L{lat}"]["latency"] = lat
         out[f"fleet_L{lat}_over_fleet_seconds"] = (out[f"fleet_L{lat}"]["seconds"] /
                                                    out["fleet"]["seconds"])
+        for k in losses:
+            r = out[f"fleet_L{lat}_loss{k}"]
+            tr = last[f"fleet_L{lat}_loss{k}"][1]
+            st = tr.status()
+            timed_out = (st["state"] == L.TRIAL_TERMINATE) & (st["last_state"] == L.TRIAL_WAITING)
+            r.update(latency=lat, loss=k, bids_lost=int(tr.n_lost.sum().item()),
+                     assignment_timeout_share=float(timed_out.mean()),
+                     seconds_over_delay=r["seconds"] / out[f"fleet_L{lat}"]["seconds"])
     return out
 
 
@@ -120,6 +135,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=500)
     ap.add_argument("--latency", default="", help="uniform link latencies in ticks, "
                                                   "comma-separated (default: none)")
+    ap.add_argument("--loss", default="", help="loss thresholds 0..65535, comma-separated: "
+                    "acl_fleet_lossy_trial_batch at each --latency and each of these")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fleet_trial", "trials.json"))
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -127,7 +144,8 @@ def main():
     for s in a.shapes.split(","):
         n, B = (int(x) for x in s.split("x"))
         r = bench(n, B, a.reps, a.warmup, a.max_steps, a.chunk, dev,
-                  [int(x) for x in a.latency.split(",") if x])
+                  [int(x) for x in a.latency.split(",") if x],
+                  [int(x) for x in a.loss.split(",") if x])
         print(json.dumps(r), flush=True)
         res.append(r)
     doc = dict(device=torch.cuda.get_device_name(dev), reps=a.reps, warmup=a.warmup,

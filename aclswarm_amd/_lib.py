@@ -45,6 +45,7 @@ EXPORTS = (
     "acl_fleet_delay_trial_batch",
     "acl_fleet_lossy_auction_batch", "acl_fleet_lossy_episode_batch",
     "acl_fleet_lossy_trial_batch",
+    "acl_fleet_localize_batch", "acl_fleet_est_auction_batch",
     "acl_default_episode_params", "acl_episode_workspace_bytes", "acl_episode_batch",
     "acl_default_trial_params", "acl_trial_workspace_bytes", "acl_trial_init", "acl_trial_batch",
     "acl_fleet_trial_workspace_bytes", "acl_fleet_trial_init", "acl_fleet_trial_batch",
@@ -166,6 +167,25 @@ class FleetLossyArgs(ct.Structure):
     _fields_ = [("delay", FleetDelayArgs), ("link", FleetLoss)]
 
 
+FLEET_LOC_BAD_ROW = 0x8  # acl_fleet_localize_status_t::flags: a row is no permutation
+
+
+class FleetLocalizeArgs(ct.Structure):
+    """acl_fleet_localize_args_t (added within ABI 11): per-vehicle position
+    estimates by gossip (localization_ros.cpp, vehicle_tracker.cpp)."""
+    _fields_ = [(n, ct.c_int32) for n in ("B", "rounds", "q_rounds")] + [
+        (n, ct.c_void_p) for n in ("fidx", "Pt", "q", "stamp", "est", "round", "loss", "seed",
+                                   "n_lost", "status")]
+
+
+class FleetEstArgs(ct.Structure):
+    """acl_fleet_est_args_t (added within ABI 11): the lossy fleet auction whose
+    START reads vehicle v's own snapshot est[b][v]."""
+    _fields_ = [("lossy", FleetLossyArgs), ("est", ct.c_void_p)]
+
+
+FLEET_LOCALIZE_STATUS_DTYPE = np.dtype(
+    [(k, "<i4") for k in ("rounds_run", "n_unknown", "max_age", "flags")])
 FLEET_STATUS_DTYPE = np.dtype([(k, "<i4") for k in ("ticks_run", "n_open", "n_queued", "flags")])
 
 
@@ -409,6 +429,10 @@ def lib():
     for fn, args in (("acl_fleet_lossy_auction_batch", FleetLossyArgs),
                      ("acl_fleet_lossy_episode_batch", FleetLossyEpisodeArgs),
                      ("acl_fleet_lossy_trial_batch", FleetLossyTrialArgs)):
+        getattr(L, fn).argtypes = [ct.POINTER(Formations), ct.POINTER(args), VP]
+        getattr(L, fn).restype = ct.c_int
+    for fn, args in (("acl_fleet_localize_batch", FleetLocalizeArgs),
+                     ("acl_fleet_est_auction_batch", FleetEstArgs)):
         getattr(L, fn).argtypes = [ct.POINTER(Formations), ct.POINTER(args), VP]
         getattr(L, fn).restype = ct.c_int
     L.acl_write_assignment_log.argtypes = [ct.c_char_p, I32, VP, VP, VP, VP, VP, VP]

@@ -53,6 +53,7 @@
 #include "common.h"
 #include "cbaa_select_dev.h"  // step_select
 #include "fleet_dev.h"        // FleetMeta, fleet_layout, role_phys, the table helpers
+#include "fleet_links_dev.h"  // fleet_sub_mask, fleet_link_hash, uniform_u64
 #include "own_row_dev.h"      // own_row_check, own_row_align
 
 #include "../../include/aclswarm_amd.h"
@@ -108,13 +109,23 @@ struct FleetLossParams : FleetParams {
   int32_t* n_lost;       // [B][n]
 };
 
-template <bool Lo>
+// The own-estimate instantiations' argument: the lossy one and the vehicles'
+// snapshots. A type of its own again, for the same reason.
+struct FleetEstParams : FleetLossParams {
+  const double* est;  // [B][n][n][3]: est[b][v] is vehicle v's snapshot
+};
+
+template <bool Lo, bool E = false>
 struct FleetKernelParams {
   using type = FleetParams;
 };
 template <>
-struct FleetKernelParams<true> {
+struct FleetKernelParams<true, false> {
   using type = FleetLossParams;
+};
+template <>
+struct FleetKernelParams<true, true> {
+  using type = FleetEstParams;
 };
 
 // What the delay instantiations stage in LDS on top of the kernel's own: every
@@ -191,66 +202,16 @@ __device__ __forceinline__ void mask_set(unsigned long long (&m)[2], int u) {
   else m[0] |= 1ull << (u & 63);
 }
 
-__device__ __forceinline__ unsigned long long uniform_u64(unsigned long long x) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)x);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(x >> 32));
-  return ((unsigned long long)hi << 32) | lo;
-}
-
-// The senders vehicle w subscribes to under its row u[] (a permutation) from
-// its point i: { u[j] : adj(i, j) } as a mask over vehicle ids
-// (connectToNeighbors, coordination_ros.cpp:392-428).
-template <int S>
-__device__ __forceinline__ void fleet_sub_mask(const unsigned long long* adjrow, const int (&u)[S],
-                                               int n, int lane, unsigned long long (&sub)[2]) {
-  unsigned w0 = 0u, w1 = 0u, w2 = 0u, w3 = 0u;
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    const int j = lane + 64 * s;
-    if (j < n && ((adjrow[s] >> lane) & 1ull)) {
-      const unsigned bit = 1u << (u[s] & 31);
-      const int wd = u[s] >> 5;
-      if (wd == 0) w0 |= bit;
-      else if (wd == 1) w1 |= bit;
-      else if (wd == 2) w2 |= bit;
-      else w3 |= bit;
-    }
-  }
-  w0 = wave_or_u32(w0);
-  w1 = wave_or_u32(w1);
-  if (S > 1) {
-    w2 = wave_or_u32(w2);
-    w3 = wave_or_u32(w3);
-  }
-  sub[0] = ((unsigned long long)w1 << 32) | w0;
-  sub[1] = ((unsigned long long)w3 << 32) | w2;
-}
-
-// link_hash of include/aclswarm_amd.h after its first word: h0 is the state
-// that (seed, receiver, sender) alone give, the same for every bid of a link.
-__device__ __forceinline__ unsigned fleet_link_hash0(unsigned seed, int w, int u) {
-  unsigned h = (seed ^ (((unsigned)w << 16) | (unsigned)u)) * 0x9E3779B1u;
-  return h ^ (h >> 15);
-}
-
-__device__ __forceinline__ unsigned fleet_link_hash(unsigned h, int pub, int iter) {
-  h = (h ^ (unsigned)pub) * 0x9E3779B1u;
-  h ^= h >> 15;
-  h = (h ^ (unsigned)iter) * 0x9E3779B1u;
-  h ^= h >> 15;
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  return h ^ (h >> 16);
-}
-
 // Lo (with D only; acl_fleet_lossy_auction_batch): seeded per-link message
 // loss, a decision in the delay delivery loop and nothing else.
-template <int S, bool D, bool Lo = false>
+// E (with Lo only; acl_fleet_est_auction_batch): a START of vehicle v reads
+// the vehicle's own snapshot est[b][v] where the others read q[b], and
+// nothing else.
+template <int S, bool D, bool Lo = false, bool E = false>
 __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
-    fleet_auction_kernel(const typename FleetKernelParams<Lo>::type P) {
+    fleet_auction_kernel(const typename FleetKernelParams<Lo, E>::type P) {
   static_assert(D || !Lo, "loss is a decision of the delay delivery loop");
+  static_assert(Lo || !E, "the own-estimate entry is the lossy entry with START changed");
   constexpr int W = FleetWaves<S>::value;
   __shared__ FleetMeta meta_s[kFleetMaxN];
   __shared__ unsigned long long sub_s[kFleetMaxN][2];
@@ -415,7 +376,9 @@ __global__ void __launch_bounds__(64 * FleetWaves<S>::value)
           const int j = lane + 64 * s;
           u[s] = j < n ? (int)row[j] : 0;
         }
-        const double* qs = P.q + vb * 3;
+        const double* qs;  // the snapshot this START reads
+        if constexpr (E) qs = P.est + (vb + v) * n * 3;
+        else qs = P.q + vb * 3;
         double o[6];
         own_row_align<S>(adjf + (size_t)i * NW, i, pf, qs, u, n, lane, st, o);
         const double qx = qs[3 * v], qy = qs[3 * v + 1], qz = qs[3 * v + 2];
@@ -912,7 +875,8 @@ static acl_status_t fleet_error(const char* entry, const char* what) {
 // The argument checks the two entries share; *launch says whether anything
 // is left to do (B > 0). The workspace size is the entry's own check.
 static acl_status_t fleet_check(const char* entry, const acl_formations_t* F,
-                                const acl_fleet_auction_args_t* a, bool* launch) {
+                                const acl_fleet_auction_args_t* a, bool* launch,
+                                bool reads_q = true) {
   *launch = false;
   if (!F || !a) return fleet_error(entry, "null argument");
   const int n = F->n;
@@ -927,7 +891,7 @@ static acl_status_t fleet_check(const char* entry, const acl_formations_t* F,
       !a->done_tick || !a->vflags || !a->n_thrown || !a->n_tally || !a->queue_len || !a->status ||
       !a->workspace)
     return fleet_error(entry, "required pointer is NULL");
-  if (a->cmd && !a->q) return fleet_error(entry, "cmd is given and q is NULL");
+  if (reads_q && a->cmd && !a->q) return fleet_error(entry, "cmd is given and q is NULL");
   if (a->cmd && a->ticks < 1)
     return fleet_error(entry, "a call with cmd must run at least one tick");
   *launch = true;
@@ -951,14 +915,14 @@ static FleetParams fleet_params(const acl_formations_t* F, const acl_fleet_aucti
   return P;
 }
 
-template <bool D, bool Lo = false>
-static acl_status_t fleet_launch(const typename FleetKernelParams<Lo>::type& P, void* stream) {
+template <bool D, bool Lo = false, bool E = false>
+static acl_status_t fleet_launch(const typename FleetKernelParams<Lo, E>::type& P, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (P.n <= 64)
-    hipLaunchKernelGGL((fleet_auction_kernel<1, D, Lo>), dim3(P.B),
+    hipLaunchKernelGGL((fleet_auction_kernel<1, D, Lo, E>), dim3(P.B),
                        dim3(64 * FleetWaves<1>::value), 0, s, P);
   else
-    hipLaunchKernelGGL((fleet_auction_kernel<2, D, Lo>), dim3(P.B),
+    hipLaunchKernelGGL((fleet_auction_kernel<2, D, Lo, E>), dim3(P.B),
                        dim3(64 * FleetWaves<2>::value), 0, s, P);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return acl__set_error(hipGetErrorString(e));
@@ -981,14 +945,17 @@ extern "C" acl_status_t acl_fleet_auction_batch(const acl_formations_t* F,
 
 namespace acl_amd {
 
-// acl_fleet_delay_auction_batch, and with link acl_fleet_lossy_auction_batch:
-// the same checks in the same order, then link's own.
+// acl_fleet_delay_auction_batch, with link acl_fleet_lossy_auction_batch, and
+// with own_est (the entry reads est, which may still be NULL, instead of q)
+// acl_fleet_est_auction_batch: the same checks in the same order, then link's
+// own, then est.
 static acl_status_t fleet_delay_run(const char* entry, const acl_formations_t* F,
                                     const acl_fleet_delay_args_t* d,
-                                    const acl_fleet_loss_t* link, void* stream) {
+                                    const acl_fleet_loss_t* link, void* stream,
+                                    bool own_est = false, const double* est = nullptr) {
   const acl_fleet_auction_args_t* a = &d->base;
   bool launch;
-  const acl_status_t st = fleet_check(entry, F, a, &launch);
+  const acl_status_t st = fleet_check(entry, F, a, &launch, !own_est);
   if (st != ACL_OK) return st;
   if (d->max_lat < 1 || d->max_lat > kFleetMaxLat)
     return fleet_error(entry, "max_lat out of range [1, 64]");
@@ -997,6 +964,7 @@ static acl_status_t fleet_delay_run(const char* entry, const acl_formations_t* F
   if (link && !link->loss) return fleet_error(entry, "loss is NULL");
   if (link && !link->seed) return fleet_error(entry, "seed is NULL");
   if (link && !link->n_lost) return fleet_error(entry, "n_lost is NULL");
+  if (own_est && a->cmd && !est) return fleet_error(entry, "cmd is given and est is NULL");
   if (a->workspace_bytes < acl_fleet_delay_workspace_bytes(F->n, a->B, a->queue_cap, d->max_lat))
     return fleet_error(entry, "workspace_bytes is too small (acl_fleet_delay_workspace_bytes)");
   FleetParams P = fleet_params(F, a);
@@ -1008,7 +976,11 @@ static acl_status_t fleet_delay_run(const char* entry, const acl_formations_t* F
   PL.loss = link->loss;
   PL.seed = link->seed;
   PL.n_lost = link->n_lost;
-  return fleet_launch<true, true>(PL, stream);
+  if (!own_est) return fleet_launch<true, true>(PL, stream);
+  FleetEstParams PE;
+  static_cast<FleetLossParams&>(PE) = PL;
+  PE.est = est;
+  return fleet_launch<true, true, true>(PE, stream);
 }
 
 }  // namespace acl_amd
@@ -1027,4 +999,11 @@ extern "C" acl_status_t acl_fleet_lossy_auction_batch(const acl_formations_t* F,
   static const char entry[] = "acl_fleet_lossy_auction_batch";
   if (!l) return acl_amd::fleet_error(entry, "null argument");
   return acl_amd::fleet_delay_run(entry, F, &l->delay, &l->link, stream);
+}
+
+extern "C" acl_status_t acl_fleet_est_auction_batch(const acl_formations_t* F,
+                                                    const acl_fleet_est_args_t* e, void* stream) {
+  static const char entry[] = "acl_fleet_est_auction_batch";
+  if (!e) return acl_amd::fleet_error(entry, "null argument");
+  return acl_amd::fleet_delay_run(entry, F, &e->lossy.delay, &e->lossy.link, stream, true, e->est);
 }

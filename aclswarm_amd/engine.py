@@ -459,6 +459,7 @@ class _LossyLinks:
 
     _loss = None
     _loss_seed = None
+    _no_loss = None  # (loss 0, seed 0) of a FleetAuction.run(est=) without loss
     n_lost = None
 
     @staticmethod
@@ -574,7 +575,10 @@ class FleetAuction(_LossyLinks):
     that is due on link (u -> w) is lost with probability loss[b][w][u] /
     65536 by a hash of (loss_seed[b], w, u, publication tick, iter): loss and
     loss_seed as _LossyLinks takes them. With latency None every link takes 1
-    tick, on the delay entry's workspace. The object owns n_lost."""
+    tick, on the delay entry's workspace. The object owns n_lost.
+
+    run(..., est=) runs acl_fleet_est_auction_batch: a START of vehicle v reads
+    its own snapshot est[b][v] (FleetLocalization.est) instead of q[b]."""
 
     def __init__(self, table, fidx, Pt=None, queue_cap=None, max_iter=0, latency=None,
                  max_latency=None, loss=None, loss_seed=None):
@@ -665,12 +669,18 @@ class FleetAuction(_LossyLinks):
                                                                self.max_latency))
         return int(L.lib().acl_fleet_workspace_bytes(self.n, self.B, self.queue_cap))
 
-    def run(self, ticks, q=None, cmd=None, history=False, stream=None):
+    def run(self, ticks, q=None, cmd=None, history=False, stream=None, est=None):
         """Apply the commands cmd [B][n] u8 (FLEET_NONE / FLEET_START /
         FLEET_FLUSH of _lib; None: carry on) with the snapshot q [B][n][3]
         f64 that START reads, then run up to `ticks` ticks (each swarm stops
         at its quiescence). With history=True returns {"biditer": [ticks][B]
-        [n] i32, "open": [ticks][B][n] u8} device tensors, else None."""
+        [n] i32, "open": [ticks][B][n] u8} device tensors, else None.
+
+        est [B][n][n][3] f64 (vehicle v's own snapshot est[b][v]) selects
+        acl_fleet_est_auction_batch: START reads est and q is ignored. That
+        entry lives on the workspace of the entries with latency: an object
+        constructed without latency or loss takes latency 1 on every link if
+        it has not run yet (loss 0 is filled in for the call)."""
         B, n, dev = self.B, self.n, self.device
         ticks = int(ticks)
         if ticks < 0:
@@ -680,13 +690,21 @@ class FleetAuction(_LossyLinks):
             want["q"] = (q, (torch.float64,), (B, n, 3))
         if cmd is not None:
             want["cmd"] = (cmd, (torch.uint8,), (B, n))
+        if est is not None:
+            want["est"] = (est, (torch.float64,), (B, n, n, 3))
         self._check("FleetAuction.run", want, dev)
-        if cmd is not None and q is None:
+        if cmd is not None and q is None and est is None:
             raise ValueError("FleetAuction.run: cmd is given without the snapshot q")
+        if est is not None and self.latency is None and self.ws is not None:
+            raise ValueError("FleetAuction.run: est needs the workspace of the entries with "
+                             "latency; construct the object with latency or loss, or pass est "
+                             "from the first run on")
         if cmd is not None and ticks < 1:
             raise ValueError("FleetAuction.run: a run with cmd must run at least one tick")
         if dev.type != "cuda":
             raise ValueError(f"FleetAuction.run: the tensors must be on a CUDA device, not {dev}")
+        if est is not None and self.latency is None:  # (nothing has run: the delay layout)
+            self.latency, self.max_latency = self._latency(1, None, B, n, dev)
         if self.ws is None:
             self.ws = torch.zeros(self.workspace_bytes(), dtype=torch.uint8, device=dev)
         hist = None
@@ -715,7 +733,25 @@ class FleetAuction(_LossyLinks):
             stream = torch.cuda.current_stream(dev).cuda_stream
         if self.latency is not None:
             d.lat, d.max_lat = self.latency.data_ptr(), self.max_latency
-        if self._loss is not None:
+        if est is not None:
+            ea = L.FleetEstArgs()
+            ct.memmove(ct.byref(ea.lossy), ct.byref(lo), ct.sizeof(lo))
+            if self._loss is not None:
+                self._link(ea.lossy.link)
+            else:  # loss 0 on every link, for this call
+                if self._no_loss is None:
+                    self._no_loss = (self._loss_tensor("FleetAuction.run", 0, B, n, dev),
+                                     self._seed_tensor("FleetAuction.run", 0, B, dev))
+                if self.n_lost is None:
+                    self.n_lost = torch.zeros((B, n), dtype=torch.int32, device=dev)
+                ea.lossy.link.loss = self._no_loss[0].data_ptr()
+                ea.lossy.link.seed = self._no_loss[1].data_ptr()
+                ea.lossy.link.n_lost = self.n_lost.data_ptr()
+            ea.est = est.data_ptr()
+            L.check(L.lib().acl_fleet_est_auction_batch(ct.byref(F), ct.byref(ea),
+                                                        ct.c_void_p(stream)),
+                    "acl_fleet_est_auction_batch")
+        elif self._loss is not None:
             self._link(lo.link)
             L.check(L.lib().acl_fleet_lossy_auction_batch(ct.byref(F), ct.byref(lo),
                                                           ct.c_void_p(stream)),
@@ -734,6 +770,89 @@ class FleetAuction(_LossyLinks):
         array [B] (ticks_run, n_open, n_queued, flags); synchronises."""
         arr = np.ascontiguousarray(self._status.cpu().numpy())
         return arr.view(L.FLEET_STATUS_DTYPE).reshape(-1)
+
+
+class FleetLocalization(_LossyLinks):
+    """acl_fleet_localize_batch (added within ABI 11): B swarms of n <= 128
+    VehicleTrackers (localization_ros.cpp, vehicle_tracker.cpp) advanced round
+    by round on the device, one launch per run(). A round is one tracking_dt
+    (20 ms): every vehicle refreshes its own entry from the true positions,
+    publishes its table of (stamp, position) and merges the published tables of
+    the neighbours it subscribes to under its own row, an entry at a time, iff
+    the stamp is strictly later; include/aclswarm_amd.h states the model.
+
+    fidx [B] i32 on the table's device; Pt [B][n][n] int16 (uint16 bits),
+    vehicle w's own row (None: identity rows). Pt is NOT copied: it may be the
+    Pt tensor of a FleetAuction, so that adopted rows rewire the gossip.
+    loss / loss_seed as _LossyLinks takes them (a table on link u -> w is lost
+    by the hash of (seed, w, u, round, 0xFFFFFFFF)). The object owns est
+    [B][n][n][3] f64, stamp [B][n][n] i32, round [B] i32, n_lost and the
+    status; all zero: freshly constructed trackers. Raises ValueError on a
+    malformed argument before anything runs."""
+
+    latency = 1  # (_LossyLinks: loss may be set on any object)
+
+    def __init__(self, table, fidx, Pt=None, loss=None, loss_seed=None):
+        what = "FleetLocalization"
+        n = table.n
+        if n < 1 or n > L.FLEET_MAX_N:
+            raise ValueError(f"{what}: n = {n} out of range [1, {L.FLEET_MAX_N}]")
+        if not isinstance(fidx, torch.Tensor) or fidx.dim() != 1:
+            raise ValueError(f"{what}: fidx must be a torch tensor of shape (B,)")
+        B = int(fidx.shape[0])
+        dev = table.p.device
+        want = {"fidx": (fidx, (torch.int32,), (B,))}
+        if Pt is not None:
+            want["Pt"] = (Pt, (torch.int16, torch.uint16), (B, n, n))
+        FleetAuction._check(what, want, dev)
+        if B < 1:
+            raise ValueError(f"{what}: fidx is empty")
+        if loss is None and loss_seed is not None:
+            raise ValueError(f"{what}: loss_seed is given without loss")
+        self.table, self.fidx, self.n, self.B, self.device = table, fidx, n, B, dev
+        self._loss_setup(what, loss, loss_seed, B, n, dev)
+        if Pt is None:
+            Pt = torch.arange(n, dtype=torch.int16, device=dev).repeat(B, n, 1)
+        self.Pt = Pt
+        self.est = torch.zeros((B, n, n, 3), dtype=torch.float64, device=dev)
+        self.stamp = torch.zeros((B, n, n), dtype=torch.int32, device=dev)
+        self.round = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self._status = torch.zeros((B, 4), dtype=torch.int32, device=dev)
+
+    def run(self, rounds, q, stream=None):
+        """`rounds` rounds from the true positions q: [B][n][3] f64 (the same
+        snapshot every round) or [rounds][B][n][3] (one per round)."""
+        B, n, dev = self.B, self.n, self.device
+        what = "FleetLocalization.run"
+        if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)) or rounds < 0:
+            raise ValueError(f"{what}: rounds = {rounds!r} must be an int >= 0")
+        rounds = int(rounds)
+        if not isinstance(q, torch.Tensor) or q.dim() not in (3, 4):
+            raise ValueError(f"{what}: q must be a tensor of shape ({B}, {n}, 3) or "
+                             f"({rounds}, {B}, {n}, 3)")
+        shape = (B, n, 3) if q.dim() == 3 else (rounds, B, n, 3)
+        FleetAuction._check(what, {"q": (q, (torch.float64,), shape)}, dev)
+        if dev.type != "cuda":
+            raise ValueError(f"{what}: the tensors must be on a CUDA device, not {dev}")
+        a = L.FleetLocalizeArgs()
+        a.B, a.rounds, a.q_rounds = B, rounds, 1 if q.dim() == 3 else rounds
+        a.fidx, a.Pt, a.q = self.fidx.data_ptr(), self.Pt.data_ptr(), q.data_ptr()
+        a.stamp, a.est, a.round = self.stamp.data_ptr(), self.est.data_ptr(), self.round.data_ptr()
+        if self._loss is not None:
+            a.loss, a.seed = self._loss.data_ptr(), self._loss_seed.data_ptr()
+            a.n_lost = self.n_lost.data_ptr()
+        a.status = self._status.data_ptr()
+        F = self.table.struct()
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        L.check(L.lib().acl_fleet_localize_batch(ct.byref(F), ct.byref(a), ct.c_void_p(stream)),
+                "acl_fleet_localize_batch")
+
+    def status(self):
+        """The last run's acl_fleet_localize_status_t records as a structured
+        numpy array [B] (rounds_run, n_unknown, max_age, flags); synchronises."""
+        arr = np.ascontiguousarray(self._status.cpu().numpy())
+        return arr.view(L.FLEET_LOCALIZE_STATUS_DTYPE).reshape(-1)
 
 
 def write_assignment_log(path, q, adj, lastP, p, align_Rt, P):

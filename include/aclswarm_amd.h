@@ -811,6 +811,130 @@ typedef struct {
 acl_status_t acl_fleet_lossy_auction_batch(const acl_formations_t* formations,
                                            const acl_fleet_lossy_args_t* args, void* stream);
 
+/* ---- fleet localization: per-vehicle position estimates by gossip (added
+ * within ABI 11) -------------------------------------------------------------
+ * B swarms of n <= 128 VehicleTrackers (localization_ros.cpp,
+ * vehicle_tracker.cpp), advanced round by round in one launch (one workgroup
+ * per swarm). Every entry above starts all vehicles of swarm b from one shared
+ * snapshot q[b]; in the reference each vehicle keeps a table of (stamp,
+ * position) for all n vehicles, refreshes its own entry from its state feed
+ * (stateCb), publishes the whole table every tracking_dt and merges the tables
+ * of its formation-graph neighbours, an entry at a time, iff the received
+ * stamp is strictly later (vehicle_tracker.cpp:31-45). Added symbols:
+ * ACL_ABI_VERSION stays 11 (no existing struct or call changed).
+ *
+ * State (caller-owned, in/out; all zero: freshly constructed trackers):
+ *   stamp[b][w][i] i32   receiver w's stamp of vehicle i; 0: never heard
+ *   est[b][w][i][3] f64  receiver w's position of vehicle i
+ *   round[b] i32         the rounds run so far
+ *
+ * One round r = round[b] is one tracking_dt = 20 ms: 20 auctioneer ticks
+ * (auctioneer_dt = 1 ms) or 2 control steps (control_dt = 10 ms).
+ *   1. sense:   stamp[w][w] = r + 1 and est[w][w] takes the bits of the true
+ *               position q_r[b][w], for every vehicle w.
+ *   2. publish: every vehicle publishes its table as it stands after step 1.
+ *   3. merge:   receiver w takes part only when its row Pt[b][w] is a
+ *               permutation of 0..n-1 (a vehicle with a bad row receives
+ *               nothing, as in the auction; it still senses and publishes).
+ *               It takes the published tables of the senders u it subscribes
+ *               to under its own row -- with i the point of w, some j has
+ *               adj(i, j) and Pt[w][j] == u (connectToNeighbors,
+ *               localization_ros.cpp:152-185, the rule of the bid
+ *               subscriptions) -- except a table that is LOST:
+ *                 loss[b][w][u] == 0xFFFF ||
+ *                 (link_hash(seed[b], w, u, r, 0xFFFFFFFF) >> 16) < loss[b][w][u]
+ *               with link_hash as stated above, the round as the publication
+ *               word and 0xFFFFFFFF as the iter word: no bid has that iter, so
+ *               a table's fate is independent of every bid's under the same
+ *               seed. Each lost table counts once in n_lost[b][w]. For every i,
+ *               w's new entry is the one with the largest stamp among its own
+ *               and the PUBLISHED entries it received; on ties its own stays,
+ *               and among senders the lowest id wins. Tables already merged in
+ *               this round are never read: information travels exactly one hop
+ *               per round and the result does not depend on any visiting order.
+ *   4. round[b] += 1.
+ * Message latency is therefore below one round; that is the model's limit, as
+ * "below one tick" is acl_fleet_auction_batch's.
+ *
+ * q is [q_rounds][B][n][3] f64 with q_rounds == 1 (the same true snapshot in
+ * every round) or q_rounds == rounds (round t of the call reads q[t]). Pt is
+ * [B][n][n] u16, read only, the fleet auction's (w's own row); the caller may
+ * rewrite it between calls: subscriptions follow the row of the moment.
+ * loss / seed / n_lost as acl_fleet_loss_t; loss and seed both NULL: lossless
+ * (n_lost is then not read). rounds = a then b equals a + b.
+ *
+ * status[b] (16 bytes): rounds_run; n_unknown, the entries with stamp 0;
+ * max_age, the largest round[b] - stamp over the entries with stamp != 0 as the
+ * call returns (0 when there is none); flags: ACL_FLEET_BAD_INPUT for a fidx
+ * out of range (the swarm is untouched, round included, its n_lost does not
+ * move), ACL_FLEET_LOC_BAD_ROW when a vehicle of the swarm holds a row that is
+ * not a permutation.
+ *
+ * Argument errors, reported before any HIP call: NULL arguments, n outside
+ * [1, 128], B < 0, rounds < 0, q_rounds not in {1, rounds}, loss without seed
+ * or n_lost (or seed without loss); with B > 0: an empty formation table, a
+ * NULL adj / fidx / Pt / stamp / est / round / status, q NULL with rounds > 0.
+ * Stream-ordered, never synchronises.
+ *
+ * Not modelled: control, collision avoidance, episodes and trials from own
+ * estimates (only the auction's START reads them, below); gossip latency of
+ * whole rounds; outages of a vehicle's own state feed; n > 128; the
+ * reference's "make this smarter using Dijkstra's" TODO. */
+#define ACL_FLEET_LOC_BAD_ROW 0x8 /* localize status.flags: a row is no permutation */
+
+typedef struct {
+  int32_t rounds_run; /* rounds run in this call */
+  int32_t n_unknown;  /* entries with stamp 0 as the call returns */
+  int32_t max_age;    /* max of round - stamp over the known entries */
+  int32_t flags;      /* ACL_FLEET_BAD_INPUT, ACL_FLEET_LOC_BAD_ROW */
+} acl_fleet_localize_status_t; /* 16 bytes */
+
+typedef struct {
+  int32_t B;            /* swarms */
+  int32_t rounds;       /* >= 0 */
+  int32_t q_rounds;     /* 1 or rounds */
+  const int32_t* fidx;  /* [B] */
+  const uint16_t* Pt;   /* [B][n][n]: vehicle w's own row, formation point -> vehicle */
+  const double* q;      /* [q_rounds][B][n][3] true positions (NULL allowed with rounds == 0) */
+  int32_t* stamp;       /* [B][n][n] in/out */
+  double* est;          /* [B][n][n][3] in/out */
+  int32_t* round;       /* [B] in/out */
+  const uint16_t* loss; /* [B][n][n] receiver-major, or NULL (then seed is NULL too) */
+  const uint32_t* seed; /* [B] */
+  int32_t* n_lost;      /* [B][n] in/out, accumulated per receiver; required with loss */
+  acl_fleet_localize_status_t* status; /* [B] out */
+} acl_fleet_localize_args_t;
+
+acl_status_t acl_fleet_localize_batch(const acl_formations_t* formations,
+                                      const acl_fleet_localize_args_t* args, void* stream);
+
+/* ---- the fleet auction started from each vehicle's own estimates (added
+ * within ABI 11) -------------------------------------------------------------
+ * acl_fleet_lossy_auction_batch with one sentence changed: a START of vehicle
+ * v reads snapshot est[b][v] wherever that entry reads q[b]. est is
+ * [B][n][n][3] f64, acl_fleet_localize_batch's. Rows Pt[v][j] of est[b][v] are
+ * the closed neighbourhood the alignment reads (alignFormation under the
+ * vehicle's own row), and row v of est[b][v] is the start position: stored,
+ * and priced from in every later tally, as auctioneer.cpp:526 reads
+ * q_.row(vehid_). lossy.delay.base.q is ignored and may be NULL; est may be
+ * NULL with cmd == NULL. The workspace layout, the call rules and everything
+ * after START are the lossy entry's, and a swarm may move between
+ * acl_fleet_delay_auction_batch, acl_fleet_lossy_auction_batch and this entry
+ * from call to call. With est[b][v] == q[b] for every v this is the lossy
+ * entry bit for bit. Argument errors: the lossy entry's (without "cmd is given
+ * and q is NULL"), plus est NULL with cmd. Added symbols: ACL_ABI_VERSION
+ * stays 11.
+ *
+ * Not modelled: as for acl_fleet_localize_batch -- control, collision
+ * avoidance, episodes and trials still read one shared snapshot. */
+typedef struct {
+  acl_fleet_lossy_args_t lossy; /* lossy.delay.base.q is ignored */
+  const double* est;            /* [B][n][n][3]: est[b][v] is vehicle v's snapshot */
+} acl_fleet_est_args_t;
+
+acl_status_t acl_fleet_est_auction_batch(const acl_formations_t* formations,
+                                         const acl_fleet_est_args_t* args, void* stream);
+
 /* ---- closed-loop batched episodes ---------------------
  * B swarms flown for `steps` control periods in lockstep: the discrete-time
  * model of one vehicle's node graph (CoordinationROS + Safety) with a

@@ -45,7 +45,7 @@ EXPORTS = (
     "acl_fleet_delay_trial_batch",
     "acl_fleet_lossy_auction_batch", "acl_fleet_lossy_episode_batch",
     "acl_fleet_lossy_trial_batch",
-    "acl_fleet_localize_batch", "acl_fleet_est_auction_batch",
+    "acl_fleet_localize_batch", "acl_fleet_est_auction_batch", "acl_fleet_est_control_batch",
     "acl_default_episode_params", "acl_episode_workspace_bytes", "acl_episode_batch",
     "acl_default_trial_params", "acl_trial_workspace_bytes", "acl_trial_init", "acl_trial_batch",
     "acl_fleet_trial_workspace_bytes", "acl_fleet_trial_init", "acl_fleet_trial_batch",
@@ -184,6 +184,19 @@ class FleetEstArgs(ct.Structure):
     _fields_ = [("lossy", FleetLossyArgs), ("est", ct.c_void_p)]
 
 
+FLEET_CTL_BAD_ROW = 0x8  # acl_fleet_control_status_t::flags: a row is no permutation
+
+
+class FleetEstControlArgs(ct.Structure):
+    """acl_fleet_est_control_args_t (added within ABI 11): one control step in
+    which vehicle v reads its own table est[b][v] under its own row Pt[b][v]."""
+    _fields_ = [("B", ct.c_int32)] + [
+        (n, ct.c_void_p) for n in ("fidx", "est", "vel", "Pt", "u", "u_safe", "ca_flag",
+                                   "status")] + [("cntrl", CntrlGains), ("safety", SafetyParams)]
+
+
+FLEET_CONTROL_STATUS_DTYPE = np.dtype(
+    [(k, "<i4") for k in ("n_ca", "n_bad_rows", "reserved", "flags")])
 FLEET_LOCALIZE_STATUS_DTYPE = np.dtype(
     [(k, "<i4") for k in ("rounds_run", "n_unknown", "max_age", "flags")])
 FLEET_STATUS_DTYPE = np.dtype([(k, "<i4") for k in ("ticks_run", "n_open", "n_queued", "flags")])
@@ -432,7 +445,8 @@ def lib():
         getattr(L, fn).argtypes = [ct.POINTER(Formations), ct.POINTER(args), VP]
         getattr(L, fn).restype = ct.c_int
     for fn, args in (("acl_fleet_localize_batch", FleetLocalizeArgs),
-                     ("acl_fleet_est_auction_batch", FleetEstArgs)):
+                     ("acl_fleet_est_auction_batch", FleetEstArgs),
+                     ("acl_fleet_est_control_batch", FleetEstControlArgs)):
         getattr(L, fn).argtypes = [ct.POINTER(Formations), ct.POINTER(args), VP]
         getattr(L, fn).restype = ct.c_int
     L.acl_write_assignment_log.argtypes = [ct.c_char_p, I32, VP, VP, VP, VP, VP, VP]

@@ -39,6 +39,26 @@ __host__ __device__ inline int cal16(int x) { return (x + 15) & ~15; }
 // Lane segments of the gain kernel: a wave processes G vehicles at once, each
 // on S consecutive lanes, in `it` passes (j = s + S t), so that n columns fill
 // the 64 lanes well (n = 100: S = 20, G = 3, 5 passes, 94% of the lanes busy,
+// against 78% for one vehicle per wave).
+struct GainSeg {
+  int S, G, it;
+};
+
+__host__ __device__ inline GainSeg gain_segments(int n) {
+  GainSeg best = {64, 1, (n + 63) / 64};
+  double bu = -1.0;
+  for (int it = 1; it <= 16; ++it) {
+    const int S = (n + it - 1) / it;
+    if (S > 64) continue;
+    const int G = 64 / S;
+    const double u = (double)n * G / (64.0 * it);
+    if (u > bu + 1e-9) {
+      bu = u;
+      best = {S, G, it};
+    }
+  }
+  return best;
+}
 
 // Safety::cmdinCb saturation (safety.cpp:185-196)
 __device__ __forceinline__ void saturate(const acl_safety_params_t& sp, double& c0, double& c1,

@@ -855,6 +855,52 @@ class FleetLocalization(_LossyLinks):
         return arr.view(L.FLEET_LOCALIZE_STATUS_DTYPE).reshape(-1)
 
 
+def fleet_est_control(table, fidx, est, vel, Pt, cntrl=None, safety=None, stream=None):
+    """acl_fleet_est_control_batch (added within ABI 11): one control step of B
+    swarms of n <= 128 vehicles in which vehicle v steers on its own table
+    est[b][v] (a FleetLocalization's est, [B][n][n][3] f64) under its own row
+    Pt[b][v] ([B][n][n] int16 holding uint16 bits): DistCntrl::compute,
+    saturation and collisionAvoidance over the table's entries, an entry never
+    heard of at whatever the table holds. fidx [B] i32, vel [B][n][3] f64.
+    Returns a dict of device tensors: u, u_safe [B][n][3] f64, ca_flag [B][n]
+    u8 and status [B][4] i32 (n_ca, n_bad_rows, reserved, flags; view it with
+    _lib.FLEET_CONTROL_STATUS_DTYPE). Raises ValueError on a malformed
+    argument before anything runs."""
+    what = "fleet_est_control"
+    n = table.n
+    if n < 1 or n > L.FLEET_MAX_N:
+        raise ValueError(f"{what}: n = {n} out of range [1, {L.FLEET_MAX_N}]")
+    if not isinstance(fidx, torch.Tensor) or fidx.dim() != 1:
+        raise ValueError(f"{what}: fidx must be a torch tensor of shape (B,)")
+    B = int(fidx.shape[0])
+    dev = table.p.device
+    FleetAuction._check(what, {"fidx": (fidx, (torch.int32,), (B,)),
+                               "est": (est, (torch.float64,), (B, n, n, 3)),
+                               "vel": (vel, (torch.float64,), (B, n, 3)),
+                               "Pt": (Pt, (torch.int16, torch.uint16), (B, n, n))}, dev)
+    if dev.type != "cuda":
+        raise ValueError(f"{what}: the tensors must be on a CUDA device, not {dev}")
+    out = {
+        "u": torch.empty((B, n, 3), dtype=torch.float64, device=dev),
+        "u_safe": torch.empty((B, n, 3), dtype=torch.float64, device=dev),
+        "ca_flag": torch.empty((B, n), dtype=torch.uint8, device=dev),
+        "status": torch.zeros((B, 4), dtype=torch.int32, device=dev),
+    }
+    a = L.FleetEstControlArgs()
+    a.B = B
+    a.fidx, a.est, a.vel, a.Pt = fidx.data_ptr(), est.data_ptr(), vel.data_ptr(), Pt.data_ptr()
+    a.u, a.u_safe = out["u"].data_ptr(), out["u_safe"].data_ptr()
+    a.ca_flag, a.status = out["ca_flag"].data_ptr(), out["status"].data_ptr()
+    a.cntrl = cntrl or L.default_gains()
+    a.safety = safety or L.default_safety()
+    F = table.struct()
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    L.check(L.lib().acl_fleet_est_control_batch(ct.byref(F), ct.byref(a), ct.c_void_p(stream)),
+            "acl_fleet_est_control_batch")
+    return out
+
+
 def write_assignment_log(path, q, adj, lastP, p, align_Rt, P):
     """Auctioneer::logAssignment's binary record (auctioneer.cpp:577-597),
     host arrays: q, p [n][3]; adj [n][n] (adj[i][j] = adjmat(i,j)); lastP, P

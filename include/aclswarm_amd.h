@@ -876,9 +876,8 @@ acl_status_t acl_fleet_lossy_auction_batch(const acl_formations_t* formations,
  * NULL adj / fidx / Pt / stamp / est / round / status, q NULL with rounds > 0.
  * Stream-ordered, never synchronises.
  *
- * Not modelled: control, collision avoidance, episodes and trials from own
- * estimates (only the auction's START reads them, below); gossip latency of
- * whole rounds; outages of a vehicle's own state feed; n > 128; the
+ * Not modelled: episodes and trials from own estimates (the auction's START
+ * and one control step read them, below); gossip latency of whole rounds; outages of a vehicle's own state feed; n > 128; the
  * reference's "make this smarter using Dijkstra's" TODO. */
 #define ACL_FLEET_LOC_BAD_ROW 0x8 /* localize status.flags: a row is no permutation */
 
@@ -925,8 +924,9 @@ acl_status_t acl_fleet_localize_batch(const acl_formations_t* formations,
  * and q is NULL"), plus est NULL with cmd. Added symbols: ACL_ABI_VERSION
  * stays 11.
  *
- * Not modelled: as for acl_fleet_localize_batch -- control, collision
- * avoidance, episodes and trials still read one shared snapshot. */
+ * Not modelled: as for acl_fleet_localize_batch -- the episodes and trials
+ * still read one shared snapshot (one control step from own estimates is
+ * acl_fleet_est_control_batch, below). */
 typedef struct {
   acl_fleet_lossy_args_t lossy; /* lossy.delay.base.q is ignored */
   const double* est;            /* [B][n][n][3]: est[b][v] is vehicle v's snapshot */
@@ -934,6 +934,86 @@ typedef struct {
 
 acl_status_t acl_fleet_est_auction_batch(const acl_formations_t* formations,
                                          const acl_fleet_est_args_t* args, void* stream);
+
+/* ---- one control step from each vehicle's own estimates (added within ABI
+ * 11) ------------------------------------------------------------------------
+ * acl_control_batch's step for B swarms of n <= 128 vehicles in which vehicle
+ * v steers on its own table est[b][v] (acl_fleet_localize_batch's) under its
+ * own row Pt[b][v], as the reference does: the localization table is
+ * CoordinationROS::q_ (coordination_ros.cpp:240-250,372: DistCntrl::compute)
+ * and Safety::q_ (safety.cpp:139-148,419-427: collisionAvoidance). A vehicle
+ * therefore steers on positions k - 1 tracking periods old for a vehicle k hops
+ * away, and avoids a vehicle it has never heard of at the origin. Added
+ * symbols: ACL_ABI_VERSION stays 11 (no existing struct or call changed).
+ *
+ * Inputs: fidx [B] i32; est [B][n][n][3] f64, est[b][v][j] vehicle v's
+ * position of vehicle j; vel [B][n][3] f64; Pt [B][n][n] u16, vehicle v's own
+ * row, formation point -> vehicle; cntrl, safety. Outputs: u [B][n][3] f64
+ * (DistCntrl's command; may be NULL), u_safe [B][n][3] f64, ca_flag [B][n] u8,
+ * status [B].
+ *
+ * For vehicle v of swarm b, with T = est[b][v] and row = Pt[b][v]:
+ *   bad row    row is not a permutation of 0..n-1: u = u_safe = 0, ca_flag = 0;
+ *              the vehicle counts in n_bad_rows and the swarm's flags get
+ *              ACL_FLEET_CTL_BAD_ROW. The other vehicles are unaffected.
+ *   valid row  i is the point with row[i] == v.
+ *     u       DistCntrl::compute (distcntrl.cpp:46-102) with q_veh := T: for
+ *             every j with adj(i, j), qij = T[row[j]] - T[v]; the gain block
+ *             A_ij times qij, the two atan scale terms gated on |e_xy| >
+ *             e_xy_thr and |e_z| > e_z_thr (the formation distances by
+ *             pdistmat's Gram formula, the gates decided on the reference's
+ *             arithmetic within 1e-9 of a threshold, as acl_control_batch
+ *             decides them), times kp, plus kd (-vel[b][v]) per neighbour.
+ *             Both gain layouts (gain_planes 9 and 5; gains_tiled is not
+ *             read). The sum over the neighbours is a tree: u agrees with
+ *             the reference's order to about 1e-12 relative, not bit for bit.
+ *     u_safe  Safety::cmdinCb saturation (safety.cpp:185-196) of u, then
+ *             Safety::collisionAvoidance (safety.cpp:412-541) over T[j] - T[v]
+ *             for all j != v. An entry never heard of is whatever T holds
+ *             (the origin, from fresh trackers): it is NOT special-cased, as in
+ *             the reference. ca_flag is 1 iff collisionAvoidance modified the
+ *             command.
+ * status[b] (16 bytes): n_ca, the vehicles with ca_flag = 1; n_bad_rows; one
+ * reserved word (0); flags. A fidx out of range (-1 included) gives
+ * ACL_FLEET_BAD_INPUT, and the swarm's u, u_safe and ca_flag are zeroed.
+ *
+ * With est[b][v] == q[b] for every v and every row the inverse of one
+ * assignment P this is acl_control_batch on (q, P), the sum order apart.
+ *
+ * Argument errors, reported before any HIP call: NULL arguments, n outside
+ * [1, 128], B < 0, gain_planes not 9 (or 0) or 5; with B > 0: an empty
+ * formation table, a NULL p / adj / gains / gain_off / fidx / est / vel / Pt /
+ * u_safe / ca_flag / status. No workspace. Stream-ordered, never synchronises,
+ * no global counters.
+ *
+ * Not modelled: the closed loop on own estimates (episodes and trials still
+ * read one shared snapshot); what acl_fleet_localize_batch does not model. */
+#define ACL_FLEET_CTL_BAD_ROW 0x8 /* control status.flags: a row is no permutation */
+
+typedef struct {
+  int32_t n_ca;       /* vehicles whose command collisionAvoidance modified */
+  int32_t n_bad_rows; /* vehicles whose row is not a permutation */
+  int32_t reserved;   /* 0 */
+  int32_t flags;      /* ACL_FLEET_BAD_INPUT, ACL_FLEET_CTL_BAD_ROW */
+} acl_fleet_control_status_t; /* 16 bytes */
+
+typedef struct {
+  int32_t B;           /* swarms */
+  const int32_t* fidx; /* [B] */
+  const double* est;   /* [B][n][n][3]: est[b][v] is vehicle v's table */
+  const double* vel;   /* [B][n][3] */
+  const uint16_t* Pt;  /* [B][n][n]: vehicle v's own row, formation point -> vehicle */
+  double* u;           /* [B][n][3] out, or NULL */
+  double* u_safe;      /* [B][n][3] out */
+  uint8_t* ca_flag;    /* [B][n] out */
+  acl_fleet_control_status_t* status; /* [B] out */
+  acl_cntrl_gains_t cntrl;
+  acl_safety_params_t safety;
+} acl_fleet_est_control_args_t;
+
+acl_status_t acl_fleet_est_control_batch(const acl_formations_t* formations,
+                                         const acl_fleet_est_control_args_t* args,
+                                         void* stream);
 
 /* ---- closed-loop batched episodes ---------------------
  * B swarms flown for `steps` control periods in lockstep: the discrete-time

@@ -452,41 +452,67 @@ __device__ __forceinline__ void runner_up_walk(int n, const unsigned (&key)[NC],
 // The alignment is a chain of ~2n dependent sums per work item, ~55 items per
 // swarm at C3: inside the auction workgroup it ran on one wave while the
 // swarm's other seven waited at the barrier, for a fifth of the swarm's life.
-// align_kernel gives each swarm one wave (LDS ~6 KB: many swarms per CU) and
-// leaves, per swarm, the work items' (R, t), the item of every formation row
-// and the smallest alignment gap in the workspace (WsLayout::align); the
-// auction kernel reads them back. The arithmetic is the same code in the
-// same order (bit-identical R, t).
+// align_kernel leaves, per swarm, the work items' (R, t), the item of every
+// formation row and the smallest alignment gap in the workspace
+// (WsLayout::align); the auction kernel reads them back. The arithmetic is
+// the same code in the same order (bit-identical R, t).
+//
+// A wave's pass over the n members costs the same with 3 lanes active as
+// with 64, and a C3 swarm has 57 items on average, 47 % of them more than 64:
+// one wave per swarm ran 1.475 passes per swarm at 60 % lane use. So one
+// workgroup (kAlignWaves waves) takes kAlignS consecutive swarms: each wave
+// stages its share of the swarms (points, permutation check, work list) as a
+// wave of its own, then the group's items form one list, (swarm, item) in
+// order, that the waves run in chunks of 64 lanes (0.95 passes per swarm at
+// kAlignS = 8). A lane reads its item's adjacency row from the formation
+// table itself: LDS holds the points and the item lists only.
+#ifndef ACL_ALIGN_S
+#define ACL_ALIGN_S 8      // swarms per workgroup
+#endif
+#ifndef ACL_ALIGN_WAVES
+#define ACL_ALIGN_WAVES 4  // waves per workgroup
+#endif
+constexpr int kAlignS = ACL_ALIGN_S, kAlignWaves = ACL_ALIGN_WAVES;
+static_assert(kAlignS <= 64 * kAlignWaves, "a thread per swarm writes the group's results");
+
 struct AlignLayout {
-  int pq, adjF, items, itm, Pin, seen, misc, total;
+  int pq, pqs, items, its, seen, gap, fs, cnt, bad, total;
 };
 __host__ __device__ inline AlignLayout make_align_layout(int n) {
   AlignLayout L;
   int o = 0;
-  L.pq = o;    o = a16(o + (n + 8) * 32);  // {p.x, p.y, qf.x, qf.y} per point (padded)
-  L.adjF = o;  o = a16(o + n * 16);        // [n][2] formation rows (no diagonal)
-  L.items = o; o = a16(o + n);
-  L.itm = o;   o = a16(o + n);
-  L.Pin = o;   o = a16(o + n);
-  L.seen = o;  o = a16(o + 16);
-  L.misc = o;  o = a16(o + 16);
+  // [kAlignS] x [n + 8] {p.x, p.y, qf.x, qf.y} per point (padded). A stride
+  // that is no multiple of the 256-byte bank row: the reads of a chunk that
+  // straddles swarms go to different banks.
+  L.pqs = (n + 8) * 32;
+  if ((L.pqs & 255) == 0) L.pqs += 32;
+  L.pq = o;    o = a16(o + kAlignS * L.pqs);
+  L.its = a16(n);
+  L.items = o; o = a16(o + kAlignS * L.its);  // [kAlignS][n] u8 work lists (rows)
+  L.seen = o;  o = a16(o + kAlignS * 16);     // [kAlignS][2] u64 permutation check
+  L.gap = o;   o = a16(o + kAlignS * 8);      // [kAlignS] u64 smallest gap (bits)
+  L.fs = o;    o = a16(o + kAlignS * 4);      // [kAlignS] i32 formation
+  L.cnt = o;   o = a16(o + kAlignS * 4);      // [kAlignS] i32 items (0: bad input)
+  L.bad = o;   o = a16(o + kAlignS * 4);      // [kAlignS] i32 P_in is no permutation
   L.total = o;
   return L;
 }
 
 // The alignment work list (one wave): formation rows with an incomplete
 // closed neighbourhood ascending, then one row standing for every complete
-// one; itm[i] = the item of row i. Returns the item count.
-template <int NC>
-__device__ __forceinline__ int align_worklist(int n, const unsigned long long* adjF,
-                                              unsigned char* items, unsigned char* itm, int lane) {
+// one; itm[i] = the item of row i. Returns the item count. row(i, r0, r1):
+// formation row i's two words (no diagonal, masked past n).
+template <int NC, typename RowFn>
+__device__ __forceinline__ int align_worklist_rows(int n, RowFn&& row, unsigned char* items,
+                                                   unsigned char* itm, int lane) {
   unsigned long long cm[NC], im[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     const int i = lane + 64 * c;
     bool comp = false;
     if (i < n) {
-      unsigned long long r0 = adjF[2 * i], r1 = adjF[2 * i + 1];
+      unsigned long long r0, r1;
+      row(i, r0, r1);
       if (i < 64) r0 |= 1ull << i; else r1 |= 1ull << (i - 64);
       comp = (__popcll(r0) + __popcll(r1)) == n;
     }
@@ -516,6 +542,19 @@ __device__ __forceinline__ int align_worklist(int n, const unsigned long long* a
   }
   if (rep >= 0 && lane == 0) items[ninc] = (unsigned char)rep;
   return ninc + (rep >= 0 ? 1 : 0);
+}
+
+// (the rows staged in LDS: adjF [n][2])
+template <int NC>
+__device__ __forceinline__ int align_worklist(int n, const unsigned long long* adjF,
+                                              unsigned char* items, unsigned char* itm, int lane) {
+  return align_worklist_rows<NC>(
+      n,
+      [&](int i, unsigned long long& r0, unsigned long long& r1) {
+        r0 = adjF[2 * i];
+        r1 = adjF[2 * i + 1];
+      },
+      items, itm, lane);
 }
 
 // Eigen::umeyama (3.3.x) for work items k0 + lane (one wave, one lane per
@@ -575,77 +614,171 @@ __device__ __forceinline__ void align_chunk(int n, const double* pq, const unsig
   }
 }
 
+// align_chunk's arithmetic for one lane's item of the pooled launch
+// (align_kernel): its closed neighbourhood r (empty when !act), its swarm's
+// points pq -- per lane: the lanes of a wave may hold items of different
+// swarms, and the 16-byte reads then go to two or three addresses -- and
+// where its (R, t) go (o). Every sum is the same values in the same order as
+// align_chunk's. (A copy, not a shared body: sharing it moved instructions in
+// the n <= 64 kernels' inline alignment.)
+template <int NC>
+__device__ __forceinline__ void align_item(int n, const double* pq,
+                                           const unsigned long long (&r)[2], bool act, double* o,
+                                           double& galign) {
+  const int cnt = __popcll(r[0]) + __popcll(r[1]);
+  double s0 = -0.0, s1 = -0.0, s2 = -0.0, s3 = -0.0;
+  for_members<NC>(n, pq, r, [&](unsigned long long mk, const double (&v)[4]) {
+    masked_add4(mk, s0, s1, s2, s3, v[0], v[1], v[2], v[3]);
+  });
+  const double oon = 1.0 / (double)(act ? cnt : 1);
+  const double sm0 = s0 * oon, sm1 = s1 * oon, dm0 = s2 * oon, dm1 = s3 * oon;
+  const bool lazy = (cnt + 4) < 20;
+  const double scale = lazy ? oon : 1.0;  // 1.0 * x == x
+  const double a0 = lazy ? -0.0 : 0.0;
+  double a00 = a0, a01 = a0, a10 = a0, a11 = a0;  // a(di, sj)
+  if (__any(act && lazy)) {
+    for_members<NC>(n, pq, r, [&](unsigned long long mk, const double (&v)[4]) {
+      const double e0 = v[0] - sm0, e1 = v[1] - sm1;
+      const double d0 = scale * (v[2] - dm0), d1 = scale * (v[3] - dm1);
+      masked_add4(mk, a00, a01, a10, a11, d0 * e0, d0 * e1, d1 * e0, d1 * e1);
+    });
+  } else {  // every item in the GEMM form: scale is 1.0 and 1.0 * x == x
+    for_members<NC>(n, pq, r, [&](unsigned long long mk, const double (&v)[4]) {
+      const double e0 = v[0] - sm0, e1 = v[1] - sm1;
+      const double d0 = v[2] - dm0, d1 = v[3] - dm1;
+      masked_add4(mk, a00, a01, a10, a11, d0 * e0, d0 * e1, d1 * e0, d1 * e1);
+    });
+  }
+  if (act) {
+    // column-major sigma S(di, sj)
+    const double S[4] = {lazy ? a00 : a00 * oon, lazy ? a10 : a10 * oon,
+                         lazy ? a01 : a01 * oon, lazy ? a11 : a11 * oon};
+    const double sm[2] = {sm0, sm1}, dm[2] = {dm0, dm1};
+    double R[4], t[2], g;
+    umeyama_finish(S, sm, dm, R, t, &g);
+    galign = g < galign ? g : galign;
+    o[0] = R[0]; o[1] = R[1]; o[2] = R[2]; o[3] = R[3]; o[4] = t[0]; o[5] = t[1];
+  }
+}
+
+// swarms P.b0 + kAlignS * blockIdx.x ... of [P.b0, P.B) (the last group may
+// be partial)
 template <int NC>
 #ifndef ACL_ALIGN_OCC
 #define ACL_ALIGN_OCC 1  // min waves per SIMD align_kernel is built for (1: the compiler's choice)
 #endif
-__global__ void __launch_bounds__(64, ACL_ALIGN_OCC) align_kernel(const SolveParams P) {
+__global__ void __launch_bounds__(64 * kAlignWaves, ACL_ALIGN_OCC) align_kernel(const SolveParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int n = P.n;
   const AlignLayout L = make_align_layout(n);
-  const int b = P.b0 + blockIdx.x;
-  const int lane = threadIdx.x;
-  double* pq = reinterpret_cast<double*>(smem + L.pq);
-  unsigned long long* adjF = reinterpret_cast<unsigned long long*>(smem + L.adjF);
-  unsigned char* items = smem + L.items;
-  unsigned char* itm = smem + L.itm;
-  unsigned long long* seen = reinterpret_cast<unsigned long long*>(smem + L.seen);
-  int* misc = reinterpret_cast<int*>(smem + L.misc);
-  const int f_in = P.fidx[b];
-  if (f_in < 0 || f_in >= P.F) return;  // BAD_INPUT: the auction kernel reads nothing
-  const int f = f_in;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int bg = P.b0 + kAlignS * (int)blockIdx.x;
+  const int ns = (P.B - bg) < kAlignS ? (P.B - bg) : kAlignS;  // the group's swarms
+  unsigned long long* gapw = reinterpret_cast<unsigned long long*>(smem + L.gap);
+  int* fs = reinterpret_cast<int*>(smem + L.fs);
+  int* cnt = reinterpret_cast<int*>(smem + L.cnt);
+  int* bad = reinterpret_cast<int*>(smem + L.bad);
   const unsigned long long lastmask = (n & 63) ? ((1ull << (n & 63)) - 1ull) : ~0ull;
-  const double* gp = P.p + (size_t)f * n * 3;
-  const uint64_t* ga = P.adj + (size_t)f * n * NC;
-  if (lane < 2) seen[lane] = 0ull;
-  if (lane == 0) misc[0] = 0;
-  for (int k = lane; k < 4 * (n + 8); k += 64) pq[k] = 0.0;
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("" ::: "memory");
-  for (int j = lane; j < n; j += 64) {
-    pq[4 * j] = gp[3 * j];
-    pq[4 * j + 1] = gp[3 * j + 1];
-  }
-  for (int k = lane; k < 2 * n; k += 64) {
-    const int i = k >> 1, w = k & 1;
-    unsigned long long x = 0ull;
-    if (w < NC) {
-      x = ga[(size_t)i * NC + w];
-      if (w == NC - 1) x &= lastmask;
+  const size_t itm_off = (size_t)n * 48;  // WsLayout::align: out [n][6], itm [n], gap, count
+
+  // ---- per swarm, one wave: points, permutation check, work list ----------
+  // A swarm with a bad input (fidx out of range, P_in no permutation) gets no
+  // items and nothing written, and the wave goes on: every wave reaches the
+  // workgroup barriers below.
+  for (int s = wave; s < ns; s += kAlignWaves) {
+    const int b = bg + s;
+    double* pq = reinterpret_cast<double*>(smem + L.pq + s * L.pqs);
+    unsigned long long* seen = reinterpret_cast<unsigned long long*>(smem + L.seen) + 2 * s;
+    const int f = P.fidx[b];
+    if (lane < 2) seen[lane] = 0ull;
+    if (lane == 0) {
+      bad[s] = 0;
+      cnt[s] = 0;
+      fs[s] = f;
+      gapw[s] = (unsigned long long)__double_as_longlong(1.0);
     }
-    adjF[k] = x;
+    if (f < 0 || f >= P.F) continue;  // BAD_INPUT (wave-uniform): the auction kernel reads nothing
+    // (the padding past n: read by for_members, added by no lane)
+    if (lane < 32) pq[4 * n + lane] = 0.0;
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("" ::: "memory");
+    const double* gp = P.p + (size_t)f * n * 3;
+    const uint64_t* ga = P.adj + (size_t)f * n * NC;
+    for (int j = lane; j < n; j += 64) {
+      pq[4 * j] = gp[3 * j];
+      pq[4 * j + 1] = gp[3 * j + 1];
+    }
+    // the permutation check and q in formation order: qf[P_in[v]] = q[v]
+    for (int v = lane; v < n; v += 64) {
+      const unsigned pv = P.P_in[(size_t)b * n + v];
+      if (pv >= (unsigned)n) {
+        bad[s] = 1;
+      } else {
+        const unsigned long long bit = 1ull << (pv & 63);
+        if (atomicOr(&seen[pv >> 6], bit) & bit) bad[s] = 1;
+        const double* qv = P.q + ((size_t)b * n + v) * 3;
+        pq[4 * pv + 2] = qv[0];
+        pq[4 * pv + 3] = qv[1];
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("" ::: "memory");
+    if (bad[s]) continue;  // not a permutation: BAD_INPUT (wave-uniform)
+    unsigned char* wsa = P.ws + P.W.align + (size_t)b * P.W.align_stride;
+    const int nitems = align_worklist_rows<NC>(
+        n,
+        [&](int i, unsigned long long& r0, unsigned long long& r1) {
+          r0 = ga[(size_t)i * NC];
+          r1 = NC > 1 ? ga[(size_t)i * NC + (NC - 1)] : 0ull;
+          if (NC > 1) r1 &= lastmask; else r0 &= lastmask;
+        },
+        smem + L.items + s * L.its, wsa + itm_off, lane);
+    if (lane == 0) cnt[s] = nitems;
   }
-  // the permutation check and q in formation order: qf[P_in[v]] = q[v]
-  for (int v = lane; v < n; v += 64) {
-    const unsigned pv = P.P_in[(size_t)b * n + v];
-    if (pv >= (unsigned)n) {
-      misc[0] = 1;
+  __syncthreads();
+
+  // ---- the group's items as one list, in chunks of 64 lanes ---------------
+  int off[kAlignS + 1];
+  off[0] = 0;
+#pragma unroll
+  for (int s = 0; s < kAlignS; ++s) off[s + 1] = off[s] + (s < ns ? cnt[s] : 0);
+  const int tot = __builtin_amdgcn_readfirstlane(off[kAlignS]);
+  for (int c0 = 64 * wave; c0 < tot; c0 += 64 * kAlignWaves) {
+    const int g = c0 + lane;
+    const bool act = g < tot;
+    int s = 0;  // the last swarm that starts at or before g: it has the item
+#pragma unroll
+    for (int t = 1; t < kAlignS; ++t) s = off[t] <= g ? t : s;
+    int k = g;
+#pragma unroll
+    for (int t = 1; t < kAlignS; ++t) k = s == t ? g - off[t] : k;
+    unsigned long long r[2] = {0ull, 0ull};
+    if (act) {
+      const int i = (smem + L.items + s * L.its)[k];
+      const uint64_t* ga = P.adj + ((size_t)fs[s] * n + i) * NC;
+      r[0] = ga[0];
+      if (NC > 1) r[1] = ga[NC - 1];
+      r[NC - 1] &= lastmask;
+      if (i < 64) r[0] |= 1ull << i; else r[1] |= 1ull << (i - 64);
     } else {
-      const unsigned long long bit = 1ull << (pv & 63);
-      if (atomicOr(&seen[pv >> 6], bit) & bit) misc[0] = 1;
-      const double* qv = P.q + ((size_t)b * n + v) * 3;
-      pq[4 * pv + 2] = qv[0];
-      pq[4 * pv + 3] = qv[1];
+      s = 0;
+      k = 0;
     }
+    const double* pq = reinterpret_cast<const double*>(smem + L.pq + s * L.pqs);
+    double* o = reinterpret_cast<double*>(P.ws + P.W.align + (size_t)(bg + s) * P.W.align_stride) +
+                6 * k;
+    double galign = 1.0;
+    align_item<NC>(n, pq, r, act, o, galign);
+    // non-negative doubles order like their bits
+    if (act) atomicMin(&gapw[s], (unsigned long long)__double_as_longlong(galign));
   }
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("" ::: "memory");
-  if (misc[0]) return;  // not a permutation: BAD_INPUT (wave-uniform)
-  const int nitems = align_worklist<NC>(n, adjF, items, itm, lane);
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("" ::: "memory");
-  unsigned char* wsa = P.ws + P.W.align + (size_t)b * P.W.align_stride;
-  double* gout = reinterpret_cast<double*>(wsa);
-  double galign = 1.0;
-  for (int k0 = 0; k0 < nitems; k0 += 64) align_chunk<NC>(n, pq, adjF, items, nitems, k0, lane, gout, galign);
-  // the swarm's smallest alignment gap, the item of every row, the count
-  const unsigned long long gb =
-      ~wave_max_u64(~(unsigned long long)__double_as_longlong(galign));  // wave minimum
-  unsigned char* gitm = wsa + (size_t)n * 48;
-  for (int i = lane; i < n; i += 64) gitm[i] = itm[i];
-  if (lane == 0) {
-    *reinterpret_cast<unsigned long long*>(wsa + (size_t)n * 48 + a16(n)) = gb;
-    *reinterpret_cast<int*>(wsa + (size_t)n * 48 + a16(n) + 8) = nitems;
+  __syncthreads();
+  // per swarm: its smallest alignment gap and the item count
+  if (tid < ns && cnt[tid] > 0) {
+    unsigned char* wsa = P.ws + P.W.align + (size_t)(bg + tid) * P.W.align_stride;
+    *reinterpret_cast<unsigned long long*>(wsa + itm_off + a16(n)) = gapw[tid];
+    *reinterpret_cast<int*>(wsa + itm_off + a16(n) + 8) = cnt[tid];
   }
 }
 
@@ -1573,7 +1706,8 @@ static hipError_t launch_auction_t(const SolveParams& P, int nb, hipStream_t str
   const hipError_t ea = once.run([] {
     for (const void* k : {(const void*)auction_kernel<1, 128, FUSE, GM, MG>,
                           (const void*)auction_kernel<1, 256, FUSE, GM, MG>,
-                          (const void*)auction_kernel<2, 512, FUSE, GM, MG>}) {
+                          (const void*)auction_kernel<2, 512, FUSE, GM, MG>,
+                          (const void*)align_kernel<2>}) {
       const hipError_t e =
           hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       if (e != hipSuccess) return e;
@@ -1581,11 +1715,14 @@ static hipError_t launch_auction_t(const SolveParams& P, int nb, hipStream_t str
     return hipSuccess;
   });
   if (ea != hipSuccess) return ea;
-  // phase 1 (the alignment) as its own launch, one wave per swarm
+  // phase 1 (the alignment) as its own launch, kAlignS swarms per workgroup
   // (n <= 64: inside the auction workgroup)
-  if (P.n > 64)
-    hipLaunchKernelGGL((align_kernel<2>), dim3(nb), dim3(64), make_align_layout(P.n).total, stream,
-                       P);
+  if (P.n > 64) {
+    SolveParams A = P;
+    A.B = P.b0 + nb;  // align_kernel's swarms are [b0, B)
+    hipLaunchKernelGGL((align_kernel<2>), dim3((nb + kAlignS - 1) / kAlignS),
+                       dim3(64 * kAlignWaves), make_align_layout(P.n).total, stream, A);
+  }
   const int lds = auction_lds(P.n, FUSE);
   // (64 threads for n <= 32 measured no faster at C2: 0.091 vs 0.088 ms)
   if (P.n <= 32)

@@ -1,8 +1,9 @@
 // solve.hip -- host entry points of the batched solve (C ABI).
 //
 // acl_solve_batch enqueues, stream-ordered, over all B swarms:
-//   1. the alignment launch (n > 64): align_kernel<2> (auction.hip, one wave
-//      per swarm) for 64 < n <= 128, align_wide_kernel (solve_wide.hip, one
+//   1. the alignment launch (n > 64): align_kernel<2> (auction.hip, a
+//      workgroup per group of consecutive swarms, their items pooled into
+//      full waves) for 64 < n <= 128, align_wide_kernel (solve_wide.hip, one
 //      1 024-thread workgroup per swarm) for n > 128; n <= 64 aligns inside
 //      the auction workgroup;
 //   2. the auction launch: auction_kernel (auction.hip, n <= 128, every CBAA

@@ -484,6 +484,9 @@ def lib():
     if hasattr(L, "acl_internal_price_sweep"):  # (absent from older experiment builds)
         L.acl_internal_price_sweep.argtypes = [VP, VP, VP, ct.c_int]
         L.acl_internal_price_sweep.restype = ct.c_int
+    if hasattr(L, "acl_internal_rsq_sweep"):  # (absent from older experiment builds)
+        L.acl_internal_rsq_sweep.argtypes = [VP, VP, ct.c_int]
+        L.acl_internal_rsq_sweep.restype = ct.c_int
     if hasattr(L, "acl_internal_neighbourhoods"):  # (absent from older experiment builds)
         L.acl_internal_neighbourhoods.argtypes = [ct.c_int, ct.c_int, VP, VP, VP, ct.c_int]
         L.acl_internal_neighbourhoods.restype = ct.c_int

@@ -105,7 +105,8 @@ __host__ __device__ inline ALayout make_alayout(int n) {
   return L;
 }
 
-enum { A_NITEMS = 2, A_RCH = 3 /* [2]: a column changed in a round of that parity */ };
+enum { A_NITEMS = 2, A_RCH = 3 /* [2]: a column changed in a round of that parity */,
+       A_PBIG = 14 /* a formation coordinate is not below 1e100 in magnitude */ };
 
 // diagnostic builds (-DACL_AUCTION_STOP=k): the kernel returns after phase
 // k, for per-phase instruction counts (scripts/auction_phase_pmc.sh)
@@ -114,6 +115,11 @@ enum { A_NITEMS = 2, A_RCH = 3 /* [2]: a column changed in a round of that parit
 #endif
 #define ACL_AUCTION_STOP_AT(k) \
   if (ACL_AUCTION_STOP == (k)) return
+
+// price phase (phase 2), the A/B switch of DESIGN 4.12
+#ifndef ACL_PRICE_NANIN
+#define ACL_PRICE_NANIN 1  // NaN prices ruled out by a bound on the inputs, per wave
+#endif
 
 // the four doubles of pq[j] (broadcast LDS reads)
 __device__ __forceinline__ void load4(const double* pq, int j, double (&v)[4]) {
@@ -856,6 +862,7 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
   // until the permutation check can run.
   const bool hv = tid < n;
   bool pbad = false;  // a formation coordinate is not finite (phase 2's fast path)
+  bool pbig = false;  // ... or not below 1e100 in magnitude (phase 2's NaN test)
   unsigned pvr = 0u;
   double qx = 0.0, qy = 0.0, qz = 0.0;
   if (hv) {
@@ -868,6 +875,7 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
     for (int k = tid; k < 3 * n; k += kAB) {
       const double x = gp[k];
       pbad |= !__builtin_isfinite(x);
+      if (ACL_PRICE_NANIN) pbig |= !(fabs(x) < 1e100);
       p[k] = x;
       const int j = k / 3, comp = k - 3 * j;
       if (kInlineAlign && comp < 2) pq[4 * j + comp] = x;  // pq[j] = {p_j.xy, qf_j.xy}
@@ -910,6 +918,7 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
     *margw = (unsigned long long)__double_as_longlong(1.0);
   }
   if (__any(pbad) && lane == 0) misc[M_PINF] = 1;
+  if (ACL_PRICE_NANIN && __any(pbig) && lane == 0) misc[A_PBIG] = 1;
   if (hv) {
     // the permutation check; q in formation order: qf[P_in[v]] = q[v]
     const int v = tid;
@@ -1063,28 +1072,47 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
     const double o0 = o[0], o1 = o[1], o2 = o[2], o3 = o[3], o4 = o[4], o5 = o[5];
     const double q0 = qv[0], q1 = qv[1], q2 = qv[2];
     float* Crow = C + pv * n;
-    for (int j = j0; pact && j < n; j += per) {
-      const double px = p[3 * j], py = p[3 * j + 1], pz = p[3 * j + 2];
-      double dx, dy, dz;
-      if (pfin) {
-        dx = q0 - ((o0 * px + o1 * py) + o4);
-        dy = q1 - ((o2 * px + o3 * py) + o5);
-        dz = q2 - pz;
-      } else {
-        const double ax = ((o0 * px + o1 * py) + 0.0 * pz) + o4;
-        const double ay = ((o2 * px + o3 * py) + 0.0 * pz) + o5;
-        const double az = ((0.0 * px + 0.0 * py) + 1.0 * pz) + 0.0;
-        dx = q0 - ax; dy = q1 - ay; dz = q2 - az;
+    // A price is NaN only if its squared distance is (acl_price is finite on
+    // [0, inf]). With every formation coordinate (A_PBIG, phase 0) and this
+    // wave's own q and (R, t) entries finite and below 1e100 in magnitude, no
+    // product overflows and every difference is finite, so none of the wave's
+    // distances is NaN (a sum of squares may overflow to inf: price 0): the
+    // wave's loop needs no test per price, and p is finite. Any other wave
+    // runs the general body. (Wave-uniform: every lane tests the values its
+    // own prices read, so no barrier is needed and the waves decide alone.)
+    bool big = !(fabs(o0) < 1e100) || !(fabs(o1) < 1e100) || !(fabs(o2) < 1e100) ||
+               !(fabs(o3) < 1e100) || !(fabs(o4) < 1e100) || !(fabs(o5) < 1e100) ||
+               !(fabs(q0) < 1e100) || !(fabs(q1) < 1e100) || !(fabs(q2) < 1e100);
+    const bool bounded = ACL_PRICE_NANIN && !__any(big) && misc[A_PBIG] == 0;
+    auto tasks = [&](auto general) {
+      constexpr bool kGen = decltype(general)::value;
+      for (int j = j0; pact && j < n; j += per) {
+        const double px = p[3 * j], py = p[3 * j + 1], pz = p[3 * j + 2];
+        double dx, dy, dz;
+        if (!kGen || pfin) {
+          dx = q0 - ((o0 * px + o1 * py) + o4);
+          dy = q1 - ((o2 * px + o3 * py) + o5);
+          dz = q2 - pz;
+        } else {
+          const double ax = ((o0 * px + o1 * py) + 0.0 * pz) + o4;
+          const double ay = ((o2 * px + o3 * py) + 0.0 * pz) + o5;
+          const double az = ((0.0 * px + 0.0 * py) + 1.0 * pz) + 0.0;
+          dx = q0 - ax; dy = q1 - ay; dz = q2 - az;
+        }
+        const float c = acl_price((dx * dx + dy * dy) + dz * dz);  // bit-exact, see common.h
+        Crow[j] = c;
+        if (kGen) nonfin |= (c != c);
+        // strict > from max = 0 (NaN never wins, never becomes the runner-up)
+        const bool gt = c > pbest;
+        psec = gt ? pbest : (c > psec ? c : psec);
+        pbj = gt ? j : pbj;
+        pbest = gt ? c : pbest;
       }
-      const float c = acl_price((dx * dx + dy * dy) + dz * dz);  // bit-exact, see common.h
-      Crow[j] = c;
-      nonfin |= (c != c);
-      // strict > from max = 0 (NaN never wins, never becomes the runner-up)
-      const bool gt = c > pbest;
-      psec = gt ? pbest : (c > psec ? c : psec);
-      pbj = gt ? j : pbj;
-      pbest = gt ? c : pbest;
-    }
+    };
+    if (bounded)
+      tasks(std::false_type{});
+    else
+      tasks(std::true_type{});
     if (pact && pbj >= 0)
       atomicMax(&W1[pv], ((unsigned long long)__float_as_uint(pbest) << 8) |
                              (unsigned long long)(255 - pbj));
@@ -1691,6 +1719,13 @@ __global__ void price_sweep_kernel(const double* x, float* fast, float* ieee, in
   }
 }
 
+// test hook: the hardware reciprocal square root acl_price starts from, raw
+// (tests/test_gpu_price_fast.py, scripts/rsq_f64_error.py)
+__global__ void rsq_sweep_kernel(const double* x, double* r, int m) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < m) r[i] = __builtin_amdgcn_rsq(x[i]);
+}
+
 // the dynamic LDS of the auction kernel, fused or not
 static int auction_lds(int n, bool fuse) {
   const int a = make_alayout(n).total;
@@ -1755,5 +1790,11 @@ extern "C" int acl_internal_price_sweep(const double* x, float* fast, float* iee
   if (m <= 0) return 0;
   hipLaunchKernelGGL(acl_amd::price_sweep_kernel, dim3((m + 255) / 256), dim3(256), 0, 0, x, fast,
                      ieee, m);
+  return hipDeviceSynchronize() == hipSuccess ? 0 : 1;
+}
+
+extern "C" int acl_internal_rsq_sweep(const double* x, double* r, int m) {
+  if (m <= 0) return 0;
+  hipLaunchKernelGGL(acl_amd::rsq_sweep_kernel, dim3((m + 255) / 256), dim3(256), 0, 0, x, r, m);
   return hipDeviceSynchronize() == hipSuccess ? 0 : 1;
 }

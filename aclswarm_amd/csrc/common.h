@@ -369,24 +369,38 @@ __device__ __forceinline__ double acl_atan_b(double x, const double* tab) {
 
 // getPrice (auctioneer.cpp:546-549) from the squared distance x:
 // (float)(1.0 / (sqrt(x) + 1e-8)) with IEEE sqrt and division, bit for bit.
-// The fast path computes y = 1 / (sqrt(x) + 1e-8) with sqrt_nr and div_nr
-// (a few ulp of the exact double in all) and rounds it to float; that float
-// is the exact one unless a float rounding boundary (a midpoint between two
-// floats) lies within the error: the 29 mantissa bits the float drops are
-// then within 1024 ulp of their midpoint 2^28, and those lanes (about 4e-6
-// of them) -- and every x outside [1e-200, 1e60] (zero, subnormal results,
-// float underflow, inf, NaN) -- take the IEEE expression. `tests/
-// test_gpu_prices.py` sweeps it against the IEEE expression on the GPU.
+// The fast path computes y = 1 / (sqrt(x) + 1e-8) to within a bound E of the
+// exact value (below) and rounds it to float; that float is the IEEE
+// expression's (itself within 1.5 ulp of the exact value) unless a float
+// rounding boundary (a midpoint between two floats) lies within the errors:
+// the 29 mantissa bits the float drops are then within 1024 ulp of their
+// midpoint 2^28, and those lanes (about 4e-6 of them) -- and every x outside
+// (1e-6, 1e60) (zero, subnormal results, float underflow, inf, NaN) -- take
+// the IEEE expression. `tests/test_gpu_prices.py` and `tests/
+// test_gpu_price_fast.py` sweep it against the IEEE expression on the GPU.
 //
 // y = 1 / (s + 1e-8) = r / (1 + d) with r = 1/sqrt(x), d = 1e-8 r: r from the
-// hardware reciprocal square root and two Newton steps (each squares the
-// relative error, then a few ulp of rounding), y = r (1 - d + d^2) -- the
-// truncated d^3 is below 1e-15 relative for x > 1e-6 (distances above 1 mm;
-// smaller x take the IEEE expression): one transcendental and eleven
-// arithmetic instructions instead of a square root and a quotient by Newton
-// steps (two transcendentals, seventeen).
+// hardware reciprocal square root and one Newton step, y = r (1 - d + d^2) --
+// the truncated d^3 is below 1e-15 relative for x > 1e-6 (distances above
+// 1 mm; smaller x take the IEEE expression): one transcendental and eight
+// arithmetic instructions.
+//
+// E, in ulps of a double (a relative error e is at most e 2^53 ulp): the
+// instruction's largest relative error on [1e-6, 1e60] was measured at e0 =
+// 5.25e-8 = 2^-24.2 (2^20 log-uniform samples and every binade edge,
+// scripts/rsq_f64_error.py, profiles/r10_prices/rsq_f64_error.txt). The step
+// r (1 + (1 - x r^2) / 2) leaves 1.5 e0^2 = 4.2e-15, its three roundings
+// (x r, the sum into r, and 1 - t r, whose absolute error is halved) under
+// 2^-52; d^3 < 1e-15; the last fma 2^-53: 5.5e-15 relative in all, E = 50 ulp,
+// a twentieth of the window. The sweep is a sample, so the step is kept only
+// while E is at most a quarter of the window: that holds up to e0 = 2^-23
+// (E = 204 ulp), which `tests/test_gpu_price_fast.py` asserts of the
+// instruction. (A second step, ACL_PRICE_NEWTON=2: E = 12 ulp.)
 #ifndef ACL_PRICE_RSQ
 #define ACL_PRICE_RSQ 1
+#endif
+#ifndef ACL_PRICE_NEWTON
+#define ACL_PRICE_NEWTON 1  // Newton steps on the hardware reciprocal square root
 #endif
 __device__ __forceinline__ float acl_price(double x) {
 #if ACL_PRICE_RSQ
@@ -394,9 +408,11 @@ __device__ __forceinline__ float acl_price(double x) {
   double t = x * r;
   double e = __builtin_fma(-t, r, 1.0);
   r = __builtin_fma(0.5 * r, e, r);
+#if ACL_PRICE_NEWTON > 1
   t = x * r;
   e = __builtin_fma(-t, r, 1.0);
   r = __builtin_fma(0.5 * r, e, r);
+#endif
   const double d = 1e-8 * r;
   const double y = __builtin_fma(r, __builtin_fma(d, d, -d), r);
   const double lo = 1e-6;

@@ -46,6 +46,7 @@ EXPORTS = (
     "acl_fleet_lossy_auction_batch", "acl_fleet_lossy_episode_batch",
     "acl_fleet_lossy_trial_batch",
     "acl_fleet_localize_batch", "acl_fleet_est_auction_batch", "acl_fleet_est_control_batch",
+    "acl_fleet_est_episode_workspace_bytes", "acl_fleet_est_episode_batch",
     "acl_default_episode_params", "acl_episode_workspace_bytes", "acl_episode_batch",
     "acl_default_trial_params", "acl_trial_workspace_bytes", "acl_trial_init", "acl_trial_batch",
     "acl_fleet_trial_workspace_bytes", "acl_fleet_trial_init", "acl_fleet_trial_batch",
@@ -262,6 +263,24 @@ class FleetLossyEpisodeArgs(ct.Structure):
     _fields_ = [("delay", FleetDelayEpisodeArgs), ("link", FleetLoss)]
 
 
+class FleetEstEpisodeArgs(ct.Structure):
+    """acl_fleet_est_episode_args_t (added within ABI 11): the episodes on each
+    vehicle's own estimates."""
+    _fields_ = [("lossy", FleetLossyEpisodeArgs), ("track_every", ct.c_int32),
+                ("diag", ct.c_int32)] + [
+        (n, ct.c_void_p) for n in ("loc_stamp", "loc_est", "loc_round", "loc_n_lost", "xst",
+                                   "err2_hist")]
+
+
+class FleetEstEpisodeStatus(ct.Structure):
+    """acl_fleet_est_episode_status_t (40 bytes)."""
+    _fields_ = [(n, ct.c_int32) for n in ("rounds_run", "n_unknown", "max_age", "flags")] + [
+        (n, ct.c_double) for n in ("err2_own", "err2_nbr", "err2_all")]
+
+
+FLEET_EST_EPISODE_STATUS_DTYPE = np.dtype(
+    [(k, "<i4") for k in ("rounds_run", "n_unknown", "max_age", "flags")] +
+    [(k, "<f8") for k in ("err2_own", "err2_nbr", "err2_all")])
 FLEET_EPISODE_STATUS_DTYPE = np.dtype([(k, "<i4") for k in (
     "flags", "ticks_run", "n_started", "n_restarted", "n_flushed", "n_consensus", "n_adopted",
     "n_invalid")])
@@ -449,6 +468,11 @@ def lib():
                      ("acl_fleet_est_control_batch", FleetEstControlArgs)):
         getattr(L, fn).argtypes = [ct.POINTER(Formations), ct.POINTER(args), VP]
         getattr(L, fn).restype = ct.c_int
+    L.acl_fleet_est_episode_workspace_bytes.argtypes = [I32, I32, I32, I32]
+    L.acl_fleet_est_episode_workspace_bytes.restype = SZ
+    L.acl_fleet_est_episode_batch.argtypes = [ct.POINTER(Formations),
+                                              ct.POINTER(FleetEstEpisodeArgs), VP]
+    L.acl_fleet_est_episode_batch.restype = ct.c_int
     L.acl_write_assignment_log.argtypes = [ct.c_char_p, I32, VP, VP, VP, VP, VP, VP]
     L.acl_write_assignment_log.restype = ct.c_int
     L.acl_read_assignment_log.argtypes = [ct.c_char_p, ct.POINTER(I32), VP, VP, VP, VP, VP, VP]

@@ -38,6 +38,17 @@
 // __syncthreads_or), so a swarm with a bad entry is skipped like one with a
 // bad row. Nothing else differs: what is in flight lives in the fleet
 // kernel's publication logs, which the loop never touches.
+//
+// acl_fleet_est_episode_batch is the loop on each vehicle's own estimates
+// (fep_run with a FepOwn block): a gossip round of acl_fleet_localize_batch on
+// the steps s % track_every == 0, the step's ticks those of
+// acl_fleet_est_auction_batch, the control step acl_fleet_est_control_batch on
+// the vehicles' tables, all three through their public entries, and one small
+// kernel of this file between control and trajectory, on the steps that ran a
+// round or record the error:
+//   fleet_est_err_kernel    the round's localize status -> xst's integers;
+//                           <true> (diag != 0): how wrong the tables are
+//                           against the true q
 #include "common.h"
 #include "episode_dev.h"
 #include "fleet_dev.h"  // kFleetMaxLat
@@ -55,11 +66,13 @@ constexpr int kFepBlock = 256;  // fleet_handoff_kernel: 4 waves, rows v = wave,
 // region (a WsLayout: pt, mode, rows, ...), its status and outputs, and the
 // loop's own small arrays.
 struct FepLayout {
-  size_t fleet, ctl, cst, u, us, ca, cmd, vf, fidx, skip, total;
+  size_t fleet, ctl, cst, u, us, ca, cmd, vf, fidx, skip, lst, ecs, total;
 };
 
-// max_lat 0: acl_fleet_auction_batch's fleet part, else the delay layout's
-inline FepLayout fep_layout(int n, int B, int cap, int max_lat = 0) {
+// max_lat 0: acl_fleet_auction_batch's fleet part, else the delay layout's.
+// own: the status arrays of the localize and control entries follow (the
+// own-estimate entry); nothing before them moves.
+inline FepLayout fep_layout(int n, int B, int cap, int max_lat = 0, bool own = false) {
   FepLayout L;
   const size_t nb = (size_t)n, bb = (size_t)B;
   size_t o = 0;
@@ -75,6 +88,13 @@ inline FepLayout fep_layout(int n, int B, int cap, int max_lat = 0) {
   L.vf = o;    o = ws_al(o + bb * nb * 4);  // [B][n] i32: the ACL_FLEET_V_* of this step's ticks
   L.fidx = o;  o = ws_al(o + bb * 4);       // [B] i32: fidx, -1 for a BAD_INPUT swarm
   L.skip = o;  o = ws_al(o + bb);           // [B] u8: BAD_INPUT in this call
+  L.lst = o;
+  L.ecs = o;
+  if (own) {
+    o = ws_al(o + bb * sizeof(acl_fleet_localize_status_t));
+    L.ecs = o;
+    o = ws_al(o + bb * sizeof(acl_fleet_control_status_t));
+  }
   L.total = o;
   return L;
 }
@@ -283,6 +303,147 @@ __global__ void __launch_bounds__(kFepBlock) fleet_handoff_kernel(const FepArgs 
   }
 }
 
+// The own-estimate entry's arguments beside acl_fleet_lossy_episode_args_t.
+struct FepOwn {
+  int track_every, diag;
+  int32_t* loc_stamp;
+  double* loc_est;
+  int32_t* loc_round;
+  int32_t* loc_n_lost;
+  acl_fleet_est_episode_status_t* xst;
+  double* err2_hist;
+};
+
+struct EstErrArgs {
+  int n, B, k;
+  int round;  // != 0: the step ran a gossip round, lst is its status
+  const uint8_t* skip;
+  const int32_t* fidx_eff;
+  const uint64_t* adj;
+  const double* q;
+  const double* est;
+  const int32_t* stamp;
+  const uint16_t* Pt;
+  const acl_fleet_localize_status_t* lst;
+  acl_fleet_est_episode_status_t* xst;
+  double* err2_hist;
+};
+
+__device__ __forceinline__ double wave_max_gt(double m) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    // (the two 32-bit halves travel separately)
+    const int lo = __shfl_xor(__double2loint(m), o, 64);
+    const int hi = __shfl_xor(__double2hiint(m), o, 64);
+    const double y = __hiloint2double(hi, lo);
+    if (y > m) m = y;
+  }
+  return m;
+}
+
+// The estimate-error record of one step (include/aclswarm_amd.h states it):
+// with T = est[b][v] and d = T[j] - q[b][j], the maxima of
+// d2(v, j) = (dx dx + dy dy) + dz dz over the entries the controller reads.
+// One workgroup per swarm, a wave per table row (rows v = wave, wave + 4, ...),
+// lane l owns j = l and j = l + 64. Every maximum starts from +0.0 and takes
+// d2 > m only, so no NaN enters and the result is independent of the order.
+// Before that, on a step that ran a gossip round, the round's localize status
+// goes into the episode's record; kDiag = false (64 threads) does only that.
+// (A template, first used below the host loop, so that hipcc emits it after the
+// file's existing kernels and their assembly stays what it was.)
+template <bool kDiag>
+__global__ void __launch_bounds__(kFepBlock) fleet_est_err_kernel(const EstErrArgs A) {
+  __shared__ double q_s[3 * kFepMaxN];
+  __shared__ unsigned long long adj_s[2 * kFepMaxN];
+  __shared__ double d2_s[kFepBlock / 64][kFepMaxN];
+  __shared__ double red_s[kFepBlock / 64][3];
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x, n = A.n;
+  if (A.skip[b] != 0) return;  // block-uniform
+  if (A.round != 0 && tid == 0) {
+    const acl_fleet_localize_status_t ls = A.lst[b];
+    acl_fleet_est_episode_status_t* x = A.xst + b;
+    x->rounds_run += ls.rounds_run;
+    x->n_unknown = ls.n_unknown;
+    x->max_age = ls.max_age;
+  }
+  if constexpr (!kDiag) return;
+  const int lane = tid & 63, wv = tid >> 6;
+  const int NW = (n + 63) >> 6;
+  const size_t vb = (size_t)b * n;
+  {
+    const double* gq = A.q + vb * 3;
+    for (int k = tid; k < 3 * n; k += kFepBlock) q_s[k] = gq[k];
+    const uint64_t* ga = A.adj + (size_t)A.fidx_eff[b] * n * NW;  // (not skipped: fidx is valid)
+    for (int k = tid; k < n * NW; k += kFepBlock) adj_s[k] = ga[k];
+  }
+  __syncthreads();
+  double m_own = 0.0, m_nbr = 0.0, m_all = 0.0;
+  for (int v0 = 0; v0 < n; v0 += kFepBlock / 64) {  // block-uniform trip count
+    const int v = v0 + wv;
+    const bool act = v < n;
+    unsigned x[2] = {0xFFFFu, 0xFFFFu};
+    if (act) {
+      const double* T = A.est + (vb + v) * n * 3;
+      const int32_t* st = A.stamp + (vb + v) * n;
+      const uint16_t* row = A.Pt + (vb + v) * n;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int j = lane + 64 * s;
+        if (j < n) {
+          const double dx = T[3 * j] - q_s[3 * j];
+          const double dy = T[3 * j + 1] - q_s[3 * j + 1];
+          const double dz = T[3 * j + 2] - q_s[3 * j + 2];
+          const double d2 = (dx * dx + dy * dy) + dz * dz;
+          d2_s[wv][j] = d2;
+          if (j == v) {
+            if (d2 > m_own) m_own = d2;
+          } else if (st[j] != 0) {
+            if (d2 > m_all) m_all = d2;
+          }
+          x[s] = row[j];
+        }
+      }
+    }
+    __syncthreads();
+    if (act) {
+      // i: the vehicle's own point in its row
+      const unsigned long long own0 = __ballot(x[0] == (unsigned)v);
+      const unsigned long long own1 = __ballot(x[1] == (unsigned)v);
+      const int i = own0   ? __ffsll((long long)own0) - 1
+                    : own1 ? 63 + __ffsll((long long)own1)
+                           : -1;
+      if (i >= 0) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const int jj = lane + 64 * s;
+          if (jj < n && x[s] < (unsigned)n && ((adj_s[i * NW + s] >> lane) & 1ull)) {
+            const double d2 = d2_s[wv][x[s]];
+            if (d2 > m_nbr) m_nbr = d2;
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+  m_own = wave_max_gt(m_own);
+  m_nbr = wave_max_gt(m_nbr);
+  m_all = wave_max_gt(m_all);
+  if (lane == 0) {
+    red_s[wv][0] = m_own;
+    red_s[wv][1] = m_nbr;
+    red_s[wv][2] = m_all;
+  }
+  __syncthreads();
+  if (tid < 3) {
+    double m = red_s[0][tid];
+    for (int w = 1; w < kFepBlock / 64; ++w)
+      if (red_s[w][tid] > m) m = red_s[w][tid];
+    if (A.err2_hist) A.err2_hist[((size_t)A.k * A.B + b) * 3 + tid] = m;
+    double* acc = &A.xst[b].err2_own + tid;
+    if (m > *acc) *acc = m;
+  }
+}
+
 }  // namespace acl_amd
 
 extern "C" size_t acl_fleet_episode_workspace_bytes(int32_t n, int32_t B, int32_t queue_cap) {
@@ -298,15 +459,29 @@ extern "C" size_t acl_fleet_delay_episode_workspace_bytes(int32_t n, int32_t B, 
   return fep_layout(n, B, queue_cap, max_lat).total;
 }
 
+extern "C" size_t acl_fleet_est_episode_workspace_bytes(int32_t n, int32_t B, int32_t queue_cap,
+                                                        int32_t max_lat) {
+  using namespace acl_amd;
+  if (n < 1 || n > kFepMaxN || B < 1 || queue_cap < 1 || max_lat < 1 || max_lat > kFleetMaxLat)
+    return 0;
+  return fep_layout(n, B, queue_cap, max_lat, true).total;
+}
+
 namespace {
 
-// The host loop of the three entries. delay: the ticks are
+acl_status_t est_err_launch(const acl_amd::EstErrArgs& X, bool diag, hipStream_t s);
+
+// The host loop of the four entries. delay: the ticks are
 // acl_fleet_delay_auction_batch's under (lat, max_lat) on the delay workspace
 // layout; otherwise acl_fleet_auction_batch's, and lat / max_lat are unused.
 // link (with delay): the ticks are acl_fleet_lossy_auction_batch's under it.
+// own (with link): the loop on own estimates -- a gossip round every
+// track_every steps, the ticks acl_fleet_est_auction_batch's, the control step
+// acl_fleet_est_control_batch's, the error record when diag is set.
 acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
                      const acl_fleet_episode_args_t* a, const uint8_t* lat, int max_lat,
-                     const acl_fleet_loss_t* link, void* stream) {
+                     const acl_fleet_loss_t* link, void* stream,
+                     const acl_amd::FepOwn* own = nullptr) {
   using namespace acl_amd;
   static char msg[200];
   auto fail = [&](const char* what) {
@@ -328,6 +503,7 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
     return fail("auction_every, sample_every, bufflen must be >= 1 and control_dt > 0");
   if (delay && (max_lat < 1 || max_lat > kFleetMaxLat)) return fail("max_lat out of range [1, 64]");
   if (!delay) max_lat = 0;
+  if (own && own->track_every < 1) return fail("track_every < 1");
   if (B == 0 || a->steps == 0) return ACL_OK;
   if (!a->fidx || !a->q || !a->vel || !a->P || !a->Pt || !a->open || !a->invalid ||
       !a->just_received || !a->biditer || !a->price || !a->who || !a->Rt || !a->final_price ||
@@ -339,10 +515,14 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
   if (link && !link->loss) return fail("loss is NULL");
   if (link && !link->seed) return fail("seed is NULL");
   if (link && !link->n_lost) return fail("n_lost is NULL");
-  const FepLayout W = fep_layout(n, B, a->queue_cap, max_lat);
+  if (own && (!own->loc_stamp || !own->loc_est || !own->loc_round || !own->loc_n_lost ||
+              !own->xst))
+    return fail("loc_stamp, loc_est, loc_round, loc_n_lost or xst is NULL");
+  const FepLayout W = fep_layout(n, B, a->queue_cap, max_lat, own != nullptr);
   if (a->workspace_bytes < W.total)
-    return fail(delay ? "workspace_bytes is too small (acl_fleet_delay_episode_workspace_bytes)"
-                      : "workspace_bytes is too small (acl_fleet_episode_workspace_bytes)");
+    return fail(own     ? "workspace_bytes is too small (acl_fleet_est_episode_workspace_bytes)"
+                : delay ? "workspace_bytes is too small (acl_fleet_delay_episode_workspace_bytes)"
+                        : "workspace_bytes is too small (acl_fleet_episode_workspace_bytes)");
   const WsLayout WS = ws_layout(n, B);
   unsigned char* ws = (unsigned char*)a->workspace;
   unsigned char* wc = ws + W.ctl;  // the control stage's hand-off region
@@ -388,6 +568,27 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
   cs.u = u; cs.u_safe = us; cs.ca_flag = ca; cs.status = A.cst;
   cs.workspace = wc; cs.cntrl = a->cntrl; cs.safety = a->safety;
 
+  // the loop on own estimates: the three public entries' arguments
+  acl_fleet_localize_args_t lo = {};
+  acl_fleet_est_args_t ea = {};
+  acl_fleet_est_control_args_t ec = {};
+  EstErrArgs X = {};
+  if (own) {
+    acl_fleet_localize_status_t* lst =
+        reinterpret_cast<acl_fleet_localize_status_t*>(ws + W.lst);
+    lo.B = B; lo.rounds = 1; lo.q_rounds = 1; lo.fidx = fidx_eff; lo.Pt = a->Pt; lo.q = a->q;
+    lo.stamp = own->loc_stamp; lo.est = own->loc_est; lo.round = own->loc_round;
+    lo.loss = link->loss; lo.seed = link->seed; lo.n_lost = own->loc_n_lost; lo.status = lst;
+    ea.est = own->loc_est;
+    ec.B = B; ec.fidx = fidx_eff; ec.est = own->loc_est; ec.vel = a->vel; ec.Pt = a->Pt;
+    ec.u = u; ec.u_safe = us; ec.ca_flag = ca;
+    ec.status = reinterpret_cast<acl_fleet_control_status_t*>(ws + W.ecs);
+    ec.cntrl = a->cntrl; ec.safety = a->safety;
+    X.n = n; X.B = B; X.skip = A.skip; X.fidx_eff = fidx_eff; X.adj = F->adj; X.q = a->q;
+    X.est = own->loc_est; X.stamp = own->loc_stamp; X.Pt = a->Pt; X.lst = lst; X.xst = own->xst;
+    X.err2_hist = own->err2_hist;
+  }
+
   TrajParams T;
   T.n = n; T.B = B; T.q = a->q; T.vel = a->vel; T.u = u; T.us = us; T.ca = ca; T.P = a->P;
   T.est = a->est; T.ring_u = a->ring_u; T.ring_ca = a->ring_ca;
@@ -416,27 +617,55 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
     A.step = step;
     A.k = k;
     const bool auction = step % ep.auction_every == 0;
+    const bool round = own && step % own->track_every == 0;
+    if (round) {
+      // the round senses q as it stands at the start of the step
+      const acl_status_t r = acl_fleet_localize_batch(F, &lo, stream);
+      if (r != ACL_OK) return r;
+    }
     if (auction) {
       hipLaunchKernelGGL(fleet_cmd_kernel, dim3(B), dim3(kFepMaxN), 0, s, A);
       if (hipGetLastError() != hipSuccess)
         return acl__set_error("fleet_cmd_kernel launch failed");
     }
     fa.cmd = auction ? cmd : nullptr;
-    acl_status_t r = link    ? acl_fleet_lossy_auction_batch(F, &fl, stream)
-                     : delay ? acl_fleet_delay_auction_batch(F, &fd, stream)
-                             : acl_fleet_auction_batch(F, &fa, stream);
+    acl_status_t r;
+    if (own) {
+      ea.lossy = fl;
+      r = acl_fleet_est_auction_batch(F, &ea, stream);
+    } else {
+      r = link    ? acl_fleet_lossy_auction_batch(F, &fl, stream)
+          : delay ? acl_fleet_delay_auction_batch(F, &fd, stream)
+                  : acl_fleet_auction_batch(F, &fa, stream);
+    }
     if (r != ACL_OK) return r;
     hipLaunchKernelGGL(fleet_handoff_kernel<false>, dim3(B), dim3(kFepBlock), 0, s, A);
     if (hipGetLastError() != hipSuccess)
       return acl__set_error("fleet_handoff_kernel launch failed");
-    r = run_control(F, &cs, s, CTL_MIXED);
+    r = own ? acl_fleet_est_control_batch(F, &ec, stream) : run_control(F, &cs, s, CTL_MIXED);
     if (r != ACL_OK) return r;
+    if (own && (round || own->diag != 0)) {
+      X.k = k;
+      X.round = round ? 1 : 0;
+      r = est_err_launch(X, own->diag != 0, s);
+      if (r != ACL_OK) return r;
+    }
     T.step = step;
     T.k = k;
     T.tick = (step % ep.sample_every) == 0;
     hipLaunchKernelGGL(traj_kernel<true>, dim3(B), dim3(n <= 64 ? 64 : kEpBlock), 0, s, T);
     if (hipGetLastError() != hipSuccess) return acl__set_error("traj_kernel launch failed");
   }
+  return ACL_OK;
+}
+
+acl_status_t est_err_launch(const acl_amd::EstErrArgs& X, bool diag, hipStream_t s) {
+  using namespace acl_amd;
+  if (diag)
+    hipLaunchKernelGGL(fleet_est_err_kernel<true>, dim3(X.B), dim3(kFepBlock), 0, s, X);
+  else
+    hipLaunchKernelGGL(fleet_est_err_kernel<false>, dim3(X.B), dim3(64), 0, s, X);
+  if (hipGetLastError() != hipSuccess) return acl__set_error("fleet_est_err_kernel launch failed");
   return ACL_OK;
 }
 
@@ -462,4 +691,17 @@ extern "C" acl_status_t acl_fleet_lossy_episode_batch(const acl_formations_t* F,
   const acl_fleet_delay_episode_args_t* d = &l->delay;
   return fep_run("acl_fleet_lossy_episode_batch", true, F, &d->base, d->lat, d->max_lat, &l->link,
                  stream);
+}
+
+extern "C" acl_status_t acl_fleet_est_episode_batch(const acl_formations_t* F,
+                                                    const acl_fleet_est_episode_args_t* x,
+                                                    void* stream) {
+  if (!x) return acl__set_error("acl_fleet_est_episode_batch: null argument");
+  const acl_fleet_delay_episode_args_t* d = &x->lossy.delay;
+  acl_amd::FepOwn own;
+  own.track_every = x->track_every; own.diag = x->diag;
+  own.loc_stamp = x->loc_stamp; own.loc_est = x->loc_est; own.loc_round = x->loc_round;
+  own.loc_n_lost = x->loc_n_lost; own.xst = x->xst; own.err2_hist = x->err2_hist;
+  return fep_run("acl_fleet_est_episode_batch", true, F, &d->base, d->lat, d->max_lat,
+                 &x->lossy.link, stream, &own);
 }

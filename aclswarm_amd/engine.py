@@ -1230,6 +1230,128 @@ class FleetEpisode(_LossyLinks):
                 "ticks": view(self._status, L.FLEET_STATUS_DTYPE)}
 
 
+class FleetEstEpisode(FleetEpisode):
+    """The closed loop on each vehicle's own estimates
+    (acl_fleet_est_episode_batch, added within ABI 11): FleetEpisode in which
+    no vehicle reads the shared snapshot q. Every track_every control steps
+    (default 2: tracking_dt 20 ms over control_dt 10 ms) the vehicles run one
+    gossip round of FleetLocalization's model on the true q; a START aligns
+    and prices on the vehicle's own table, and the vehicle steers and avoids on
+    it. include/aclswarm_amd.h states the model and its limits.
+
+    The arguments are FleetEpisode's. The object always runs the new entry:
+    latency None means every link at 1 tick, loss None means loss 0 on every
+    link with seed 0 (tables are lost under the same loss and loss_seed as the
+    bids). It also owns the trackers loc_stamp [B][n][n] i32, loc_est
+    [B][n][n][3] f64, loc_round [B] i32 and loc_n_lost [B][n] i32 (lost
+    tables; n_lost stays the bids'), all zero: fresh trackers, and xst, the
+    acl_fleet_est_episode_status_t records. The caller may rewrite them
+    between runs. diag=True also records, per step, how wrong the tables are
+    against the true q (the err2 maxima of the header, m^2).
+    Raises ValueError on a malformed argument before anything runs."""
+
+    def __init__(self, table, fidx, q, vel, Pt=None, params=None, cntrl=None, safety=None,
+                 queue_cap=None, max_iter=0, ticks_per_step=10, latency=None, max_latency=None,
+                 loss=None, loss_seed=None, track_every=2, diag=False):
+        if isinstance(track_every, bool) or not isinstance(track_every, (int, np.integer)) or \
+                track_every < 1:
+            raise ValueError(f"FleetEstEpisode: track_every = {track_every!r} must be an int >= 1")
+        if loss is None and loss_seed is not None:
+            raise ValueError("FleetEstEpisode: loss_seed is given without loss")
+        super().__init__(table, fidx, q, vel, Pt=Pt, params=params, cntrl=cntrl, safety=safety,
+                         queue_cap=queue_cap, max_iter=max_iter, ticks_per_step=ticks_per_step,
+                         latency=1 if latency is None else latency, max_latency=max_latency,
+                         loss=0 if loss is None else loss, loss_seed=loss_seed)
+        self.track_every, self.diag = int(track_every), bool(diag)
+        B, n, dev = self.B, self.n, self.device
+        self.loc_stamp = torch.zeros((B, n, n), dtype=torch.int32, device=dev)
+        self.loc_est = torch.zeros((B, n, n, 3), dtype=torch.float64, device=dev)
+        self.loc_round = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self.loc_n_lost = torch.zeros((B, n), dtype=torch.int32, device=dev)
+        self.xst = torch.zeros((B, L.FLEET_EST_EPISODE_STATUS_DTYPE.itemsize), dtype=torch.uint8,
+                               device=dev)
+
+    def workspace_bytes(self):
+        return int(L.lib().acl_fleet_est_episode_workspace_bytes(
+            self.n, self.B, self.queue_cap, self.max_latency))
+
+    def run(self, steps, history=False, stream=None, own_estimates=True):
+        """FleetEpisode.run; with history=True and diag set the dict also holds
+        "err2" [steps][B][3] f64 (own, nbr, all; rows of BAD_INPUT swarms stay
+        0). own_estimates=False flies the steps on acl_fleet_lossy_episode_batch
+        instead (the shared snapshot q; the trackers stand still): an episode
+        may move between the two entries from run to run."""
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError(f"FleetEstEpisode.run: steps = {steps} < 0")
+        if isinstance(self.track_every, bool) or \
+                not isinstance(self.track_every, (int, np.integer)) or self.track_every < 1:
+            raise ValueError(f"FleetEstEpisode.run: track_every = {self.track_every!r} must be an "
+                             "int >= 1")
+        if self._loss is None:
+            raise ValueError("FleetEstEpisode.run: loss is None; the entry takes a loss matrix "
+                             "(0 on every link: no loss)")
+        dev, B, n = self.device, self.B, self.n
+        if self.ws is None:
+            self.ws = torch.zeros(self.workspace_bytes(), dtype=torch.uint8, device=dev)
+        hist = None
+        if history:
+            hist = {
+                "q": torch.zeros((steps, B, n, 3), dtype=torch.float64, device=dev),
+                "vel": torch.zeros((steps, B, n, 3), dtype=torch.float64, device=dev),
+                "u": torch.zeros((steps, B, n, 3), dtype=torch.float64, device=dev),
+                "ca": torch.zeros((steps, B, n), dtype=torch.uint8, device=dev),
+                "P": torch.zeros((steps, B, n), dtype=torch.int16, device=dev),
+                "vflags": torch.zeros((steps, B, n), dtype=torch.int32, device=dev),
+            }
+        x = L.FleetEstEpisodeArgs()
+        lo = x.lossy
+        d = lo.delay
+        a = d.base
+        a.B, a.step0, a.steps, a.ticks_per_step = B, self.step, steps, self.ticks_per_step
+        a.max_iter, a.queue_cap = self.max_iter, self.queue_cap
+        for k in ("fidx", "q", "vel", "P", "adopt_step", "est", "ring_u", "ring_ca", "fst") + \
+                self.FLEET_KEYS:
+            setattr(a, k, getattr(self, k).data_ptr())
+        a.status = self._status.data_ptr()
+        if hist is not None:
+            for k, v in hist.items():
+                setattr(a, k + "_hist", v.data_ptr())
+        a.workspace = self.ws.data_ptr()
+        a.workspace_bytes = self.ws.numel()
+        a.cntrl, a.safety, a.ep = self.cntrl, self.safety, self.ep
+        d.lat, d.max_lat = self.latency.data_ptr(), self.max_latency
+        self._link(lo.link)
+        F = self.table.struct()
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        if own_estimates:
+            x.track_every, x.diag = int(self.track_every), 1 if self.diag else 0
+            for k in ("loc_stamp", "loc_est", "loc_round", "loc_n_lost", "xst"):
+                setattr(x, k, getattr(self, k).data_ptr())
+            if hist is not None and self.diag:
+                hist["err2"] = torch.zeros((steps, B, 3), dtype=torch.float64, device=dev)
+                x.err2_hist = hist["err2"].data_ptr()
+            L.check(L.lib().acl_fleet_est_episode_batch(ct.byref(F), ct.byref(x),
+                                                        ct.c_void_p(stream)),
+                    "acl_fleet_est_episode_batch")
+        else:
+            L.check(L.lib().acl_fleet_lossy_episode_batch(ct.byref(F), ct.byref(lo),
+                                                          ct.c_void_p(stream)),
+                    "acl_fleet_lossy_episode_batch")
+        self.step += steps
+        return hist
+
+    def status(self):
+        """FleetEpisode.status with "estimates": the
+        acl_fleet_est_episode_status_t records (rounds_run, n_unknown, max_age,
+        flags, err2_own, err2_nbr, err2_all)."""
+        st = super().status()
+        st["estimates"] = np.ascontiguousarray(self.xst.cpu().numpy()).view(
+            L.FLEET_EST_EPISODE_STATUS_DTYPE).reshape(-1)
+        return st
+
+
 class Trial:
     """Batched Monte-Carlo trials (acl_trial_batch; supervisor.py over the
     closed loop): each swarm flies its formation sequence fseq[b] through the

@@ -876,9 +876,10 @@ acl_status_t acl_fleet_lossy_auction_batch(const acl_formations_t* formations,
  * NULL adj / fidx / Pt / stamp / est / round / status, q NULL with rounds > 0.
  * Stream-ordered, never synchronises.
  *
- * Not modelled: episodes and trials from own estimates (the auction's START
- * and one control step read them, below); gossip latency of whole rounds; outages of a vehicle's own state feed; n > 128; the
- * reference's "make this smarter using Dijkstra's" TODO. */
+ * Not modelled: trials from own estimates (the auction's START, one control
+ * step and the episodes of acl_fleet_est_episode_batch read them, below);
+ * gossip latency of whole rounds; outages of a vehicle's own state feed;
+ * n > 128; the reference's "make this smarter using Dijkstra's" TODO. */
 #define ACL_FLEET_LOC_BAD_ROW 0x8 /* localize status.flags: a row is no permutation */
 
 typedef struct {
@@ -924,9 +925,10 @@ acl_status_t acl_fleet_localize_batch(const acl_formations_t* formations,
  * and q is NULL"), plus est NULL with cmd. Added symbols: ACL_ABI_VERSION
  * stays 11.
  *
- * Not modelled: as for acl_fleet_localize_batch -- the episodes and trials
- * still read one shared snapshot (one control step from own estimates is
- * acl_fleet_est_control_batch, below). */
+ * Not modelled: as for acl_fleet_localize_batch -- the trials still read one
+ * shared snapshot (one control step from own estimates is
+ * acl_fleet_est_control_batch, the closed loop acl_fleet_est_episode_batch,
+ * below). */
 typedef struct {
   acl_fleet_lossy_args_t lossy; /* lossy.delay.base.q is ignored */
   const double* est;            /* [B][n][n][3]: est[b][v] is vehicle v's snapshot */
@@ -986,8 +988,9 @@ acl_status_t acl_fleet_est_auction_batch(const acl_formations_t* formations,
  * u_safe / ca_flag / status. No workspace. Stream-ordered, never synchronises,
  * no global counters.
  *
- * Not modelled: the closed loop on own estimates (episodes and trials still
- * read one shared snapshot); what acl_fleet_localize_batch does not model. */
+ * Not modelled: trials on own estimates (they still read one shared snapshot;
+ * the closed loop of the episodes is acl_fleet_est_episode_batch); what
+ * acl_fleet_localize_batch does not model. */
 #define ACL_FLEET_CTL_BAD_ROW 0x8 /* control status.flags: a row is no permutation */
 
 typedef struct {
@@ -1369,6 +1372,111 @@ typedef struct {
 acl_status_t acl_fleet_lossy_episode_batch(const acl_formations_t* formations,
                                            const acl_fleet_lossy_episode_args_t* args,
                                            void* stream);
+
+/* ---- the episodes on each vehicle's own estimates (added within ABI 11) -----
+ * acl_fleet_est_episode_batch is acl_fleet_lossy_episode_batch with two
+ * sentences changed and one stage added: the closed loop of
+ * acl_fleet_localize_batch, acl_fleet_est_auction_batch and
+ * acl_fleet_est_control_batch. No vehicle reads the shared snapshot q[b]: a
+ * START aligns and prices on the vehicle's own table, and the vehicle steers
+ * and avoids on it; q[b] is what the vehicles' state feeds sense and what the
+ * trajectory and the supervisor advance. Added symbols: ACL_ABI_VERSION stays
+ * 11 (no existing struct or call changed). B swarms, n <= 128, `steps` control
+ * periods, every launch stream-ordered, nothing synchronises. Per global step
+ * s = step0 + k:
+ *   0. gossip: if s % track_every == 0, one round of acl_fleet_localize_batch
+ *      on the episode's tracker state (loc_stamp, loc_est, loc_round), sensing
+ *      the true q[b] as it stands at the start of step s (q_rounds = 1).
+ *      Subscriptions follow the rows Pt of that moment. Tables are lost under
+ *      the same link.loss / link.seed as the bids; the publication word is
+ *      loc_round[b], as that entry states, so a table's fate does not depend
+ *      on how the episode is split into calls. Lost tables count in
+ *      loc_n_lost; link.n_lost stays the bids'. track_every >= 1, default 2
+ *      (tracking_dt 20 ms over control_dt 10 ms);
+ *   1. auto-auction: the commands of acl_fleet_episode_batch's step 1;
+ *   2. ticks: ticks_per_step ticks of acl_fleet_est_auction_batch under lat,
+ *      max_lat and link: a START of vehicle v reads loc_est[b][v], not q[b];
+ *   3. hand-off: as acl_fleet_episode_batch's step 3 (adopt_step, P,
+ *      vflags_hist, the fst counters, est.per_vehicle);
+ *   4. control: acl_fleet_est_control_batch on (loc_est, vel, Pt after this
+ *      step's ticks). A vehicle steers and avoids on its own table: an entry it
+ *      never heard of is the origin (from fresh trackers), and its own entry
+ *      is as old as the last round;
+ *   5. estimate-error record, only when diag != 0. With T = loc_est[b][v],
+ *      d = T[j] - q[b][j] and d2(v, j) = (dx dx + dy dy) + dz dz in fp64, one
+ *      IEEE operation each, three maxima in m^2 (squares, not roots):
+ *        err2_own  over v of d2(v, v);
+ *        err2_nbr  over v and the points jj with adj(i, jj), i the point of v
+ *                  in Pt[b][v], of d2(v, Pt[b][v][jj]): the entries DistCntrl
+ *                  reads, whatever their stamp;
+ *        err2_all  over v and j != v with loc_stamp[b][v][j] != 0: what
+ *                  collision avoidance reads of the vehicles v has heard of.
+ *      Every maximum starts from +0.0 and is taken with d2 > m: a NaN never
+ *      enters, n = 1 gives three zeros, and the value does not depend on the
+ *      order. The three go to err2_hist[k][b][0..2] when that is given, and
+ *      are folded into xst[b] with the same >;
+ *   6. makeSafeTraj and the supervisor ring on the true q, as step 5 of
+ *      acl_fleet_episode_batch.
+ * Model limits: the gossip round of step s runs before that step's commands;
+ * gossip latency is below one round; all vehicles' tracking timers fire on the
+ * same step; everything acl_fleet_lossy_episode_batch and
+ * acl_fleet_localize_batch list as limits still holds.
+ *
+ * xst[b] (40 bytes, in/out, zeroed before step 0): rounds_run accumulates;
+ * n_unknown and max_age are those of acl_fleet_localize_status_t after the
+ * last round run (updated on every step that ran a round, with diag == 0 too);
+ * the err2 fields are maxima over all steps flown with diag != 0.
+ *
+ * A swarm that the call's first hand-off flags ACL_FLEET_BAD_INPUT (a fidx out
+ * of range, a row that is no permutation, a bad latency entry) is untouched in
+ * every respect: no round and no tick run, loc_stamp / loc_est / loc_round and
+ * loc_n_lost do not move, xst[b] and its err2_hist rows are not written.
+ *
+ * Workspace: acl_fleet_est_episode_workspace_bytes(n, B, queue_cap, max_lat)
+ * bytes: the layout of acl_fleet_delay_episode_workspace_bytes with the status
+ * arrays of the localize and control entries appended; zero-filled once. On a
+ * workspace of this size an episode may move between
+ * acl_fleet_delay_episode_batch, acl_fleet_lossy_episode_batch and this entry
+ * from call to call.
+ *
+ * Argument errors, reported before any HIP call: those of
+ * acl_fleet_lossy_episode_batch on `lossy`; track_every < 1; with B > 0 and
+ * steps > 0 a NULL loc_stamp, loc_est, loc_round, loc_n_lost or xst;
+ * workspace_bytes too small (acl_fleet_est_episode_workspace_bytes).
+ *
+ * On a complete graph with track_every = 1 and no loss every table is q bit
+ * for bit after the step's round, and this is acl_fleet_lossy_episode_batch
+ * step for step, the control step's sum order apart.
+ * Not modelled: trials from own estimates; a loss matrix of its own for
+ * tables; gossip latency of whole rounds; outages of a vehicle's own state
+ * feed; n > 128. */
+typedef struct {
+  int32_t rounds_run;   /* gossip rounds, accumulated */
+  int32_t n_unknown;    /* entries with stamp 0 after the last round run */
+  int32_t max_age;      /* acl_fleet_localize_status_t.max_age of the last round run */
+  int32_t flags;        /* reserved, 0 */
+  double  err2_own;     /* maxima over all steps flown with diag != 0, m^2 */
+  double  err2_nbr;
+  double  err2_all;
+} acl_fleet_est_episode_status_t; /* 40 bytes */
+
+typedef struct {
+  acl_fleet_lossy_episode_args_t lossy; /* delay.base.q: the true positions */
+  int32_t track_every;  /* >= 1 */
+  int32_t diag;         /* != 0: step 5 runs */
+  int32_t* loc_stamp;   /* [B][n][n]    the arrays of acl_fleet_localize_args_t, in/out */
+  double*  loc_est;     /* [B][n][n][3] */
+  int32_t* loc_round;   /* [B] */
+  int32_t* loc_n_lost;  /* [B][n] lost tables; lossy.link.n_lost stays the bids' */
+  acl_fleet_est_episode_status_t* xst; /* [B] in/out, zeroed before step 0 */
+  double*  err2_hist;   /* [steps][B][3] or NULL (read only with diag) */
+} acl_fleet_est_episode_args_t;
+
+size_t acl_fleet_est_episode_workspace_bytes(int32_t n, int32_t B, int32_t queue_cap,
+                                             int32_t max_lat);
+acl_status_t acl_fleet_est_episode_batch(const acl_formations_t* formations,
+                                         const acl_fleet_est_episode_args_t* args,
+                                         void* stream);
 
 /* ---- batched Monte-Carlo trials (ABI 9; SURVEY §8f widening of row f1) ---
  * B independent trials of aclswarm_sim's supervisor (aclswarm_sim/nodes/

@@ -245,6 +245,21 @@ __device__ __forceinline__ double sqrt_nr1(double x) {
   return (x == 0.0 || __builtin_isinf(x)) ? x : s;
 }
 
+// sqrt_nr1 in two parts, for a caller that votes once per wave on the
+// arguments sqrt_nr1 returns unchanged (the fused control phase,
+// pair_e_vote): the step alone, and the test. sqrt_nr1(x) is
+// sqrt_nr1_edge(x) ? x : sqrt_nr1_step(x), bit for bit.
+__device__ __forceinline__ double sqrt_nr1_step(double x) {
+  const double y = __builtin_amdgcn_rsq(x);
+  const double g = x * y, h = 0.5 * y;
+  const double r = __builtin_fma(-g, h, 0.5);
+  return __builtin_fma(g, r, g);
+}
+
+__device__ __forceinline__ bool sqrt_nr1_edge(double x) {
+  return x == 0.0 || __builtin_isinf(x);
+}
+
 // Rows k = 0..16 of {na, nb, da, db, a_k} for acl_atan_k32:
 // atan(|x|) = a_k + atan(t), t = (na |x| + nb) / (da |x| + db), i.e.
 // t = (|x| - c_k) / (1 + c_k |x|) with c_k = tan(k pi / 32), a_k = atan(c_k);
@@ -365,6 +380,42 @@ __device__ __forceinline__ double acl_atan_b(double x, const double* tab) {
   p = ACL_FMA_K(z, p, -1.0 / 3.0);
   const double res = rw[4] + __builtin_fma(t * z, p, t);
   return (ax == __builtin_inf()) ? copysign(1.57079632679489655800e+00, x) : copysign(res, x);
+}
+
+// acl_atan_b for the fused control phase: the same bits, with the
+// infinite-argument result selected only in a wave in which some active lane
+// has one (a vote; the polynomial's value is NaN there: row 33 multiplies
+// 0 by inf), so the common path carries neither the select nor the constant.
+__device__ __forceinline__ double acl_atan_b_vote(double x, const double* tab) {
+  const double ax = fabs(x);
+  int k = (int)(__float_as_uint((float)ax) >> 21) - (123 << 2) + 1;
+  // (opaque: the clamp then yields the row index itself, in [0, 33], for the
+  // row's address; clamping the biased value instead folds the bias of 491
+  // rows into the address, a negative constant no read can take as its
+  // immediate offset, so every read of the row rebuilt its own address)
+  asm volatile("" : "+v"(k));
+  k = k < 0 ? 0 : (k > 33 ? 33 : k);
+  const double* rw = tab + 5 * k;
+  const double num = __builtin_fma(rw[0], ax, rw[1]);
+  const double den = __builtin_fma(rw[2], ax, rw[3]);
+  double r = __builtin_amdgcn_rcp(den);
+  r = __builtin_fma(__builtin_fma(-den, r, 1.0), r, r);
+  const double t = num * r;
+  const double z = t * t;
+  double p = ACL_MUL_ADD_K(z, -1.0 / 11.0, 1.0 / 9.0);
+  p = ACL_FMA_K(z, p, -1.0 / 7.0);
+  p = ACL_FMA_K(z, p, 1.0 / 5.0);
+  p = ACL_FMA_K(z, p, -1.0 / 3.0);
+  double res = rw[4] + __builtin_fma(t * z, p, t);
+  if (__any(ax == __builtin_inf())) {
+    // pi / 2 made here (volatile: a branch, not selects folded back into the
+    // common path, and no constant hoisted into a register across the loop)
+    unsigned lo, hi;
+    asm volatile("v_mov_b32 %0, 0x54442d18\n\tv_mov_b32 %1, 0x3ff921fb" : "=v"(lo), "=v"(hi));
+    const double hpi = __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+    res = (ax == __builtin_inf()) ? hpi : res;
+  }
+  return copysign(res, x);
 }
 
 // getPrice (auctioneer.cpp:546-549) from the squared distance x:

@@ -193,6 +193,33 @@ __device__ __forceinline__ void pair_e(double q0, double q1, double q2, double N
   e_z = fabs(q2) - dz;
 }
 
+// pair_e for the fused control phase (the same bits): the three one-step
+// square roots without their last select, and one vote of the wave's active
+// lanes on whether any argument is one that sqrt_nr1 returns unchanged (zero:
+// two formation points with equal xy or equal z, two vehicles with equal xy;
+// infinite: a squared distance that overflowed). Only such a wave runs the
+// selects.
+__device__ __forceinline__ void pair_e_vote(double q0, double q1, double q2, double Ni, double Nj,
+                                            double Nzi, double Nzj, double pix, double piy,
+                                            double piz, double pjx, double pjy, double pjz,
+                                            double s2, double& e_xy, double& e_z) {
+#if ACL_GAIN_FASTMATH
+  const double axy = __builtin_fma(-2.0, __builtin_fma(pix, pjx, piy * pjy), Ni + Nj);
+  const double az = __builtin_fma(-2.0, piz * pjz, Nzi + Nzj);
+  double dxy = sqrt_nr1_step(axy), dz = sqrt_nr1_step(az), dq = sqrt_nr1_step(s2);
+  if (__any(sqrt_nr1_edge(axy) || sqrt_nr1_edge(az) || sqrt_nr1_edge(s2))) {
+    asm volatile("");  // (a branch, not selects folded back into the common path)
+    dxy = sqrt_nr1_edge(axy) ? axy : dxy;
+    dz = sqrt_nr1_edge(az) ? az : dz;
+    dq = sqrt_nr1_edge(s2) ? s2 : dq;
+  }
+  e_xy = dq - dxy;
+  e_z = fabs(q2) - dz;
+#else
+  pair_e(q0, q1, q2, Ni, Nj, Nzi, Nzj, pix, piy, piz, pjx, pjy, pjz, s2, e_xy, e_z);
+#endif
+}
+
 __device__ __forceinline__ double pair_s2(double q0, double q1) {
   return __builtin_fma(q0, q0, q1 * q1);
 }

@@ -61,6 +61,25 @@
 #ifndef ACL_FUSED_PACK
 #define ACL_FUSED_PACK 1
 #endif
+// 1: the edge-case selects of the pair's square roots / of its atan behind a
+// wave vote (pair_e_vote, acl_atan_b_vote: the same bits); 0: on every pair,
+// as in the stand-alone kernels (A/B builds)
+#ifndef ACL_FUSED_SQRT_VOTE
+#define ACL_FUSED_SQRT_VOTE 1
+#endif
+#ifndef ACL_FUSED_ATAN_VOTE
+#define ACL_FUSED_ATAN_VOTE 1
+#endif
+#if ACL_FUSED_SQRT_VOTE
+#define ACL_FUSED_PAIR_E pair_e_vote
+#else
+#define ACL_FUSED_PAIR_E pair_e
+#endif
+#if ACL_FUSED_ATAN_VOTE && ACL_GAIN_FASTMATH
+#define ACL_FUSED_ATAN acl_atan_b_vote
+#else
+#define ACL_FUSED_ATAN ACL_GAIN_ATAN
+#endif
 
 namespace acl_amd {
 
@@ -439,7 +458,8 @@ __device__ __forceinline__ void pair_gain_fused(KCtlParams* Pp, int b, int f,
         const double4 bi = pi[1], bj = pj[1];  // {p.y, p.z, pn_xy, pn_z}
         const double pix = ai.w, piy = bi.x, piz = bi.y, pjx = aj.w, pjy = bj.x, pjz = bj.y;
         double e_xy, e_z;
-        pair_e(q0, q1, q2, bi.z, bj.z, bi.w, bj.w, pix, piy, piz, pjx, pjy, pjz, s2, e_xy, e_z);
+        ACL_FUSED_PAIR_E(q0, q1, q2, bi.z, bj.z, bi.w, bj.w, pix, piy, piz, pjx, pjy, pjz, s2, e_xy,
+                         e_z);
         bool gxy, gz;
         gate_decide_t<GM>(fcst(cst, FC_TXY), fcst(cst, FC_TZ), fcst(cst, FC_WIN), e_xy, e_z, q0,
                           q1, q2, bi.z, bj.z, bi.w, bj.w, pix, piy, piz, pjx, pjy, pjz, gxy, gz,
@@ -448,8 +468,8 @@ __device__ __forceinline__ void pair_gain_fused(KCtlParams* Pp, int b, int f,
         if (gxy) Fxy = fcst(cst, FC_K1XY) * (fcst(cst, FC_K2XY) * e_xy);
         if (gz) Fz = fcst(cst, FC_K1Z) * (fcst(cst, FC_K2Z) * e_z);
 #else
-        if (gxy) Fxy = fcst(cst, FC_K1XY) * ACL_GAIN_ATAN(fcst(cst, FC_K2XY) * e_xy, atab);
-        if (gz) Fz = fcst(cst, FC_K1Z) * ACL_GAIN_ATAN(fcst(cst, FC_K2Z) * e_z, atab);
+        if (gxy) Fxy = fcst(cst, FC_K1XY) * ACL_FUSED_ATAN(fcst(cst, FC_K2XY) * e_xy, atab);
+        if (gz) Fz = fcst(cst, FC_K1Z) * ACL_FUSED_ATAN(fcst(cst, FC_K2Z) * e_z, atab);
 #endif
       }
       const double f0 = Fxy * q0, f1 = Fxy * q1, f2 = Fz * q2;
@@ -555,7 +575,8 @@ __device__ __forceinline__ void pair_gain_fused(KCtlParams* Pp, int b, int f,
         const double4 bi = pi[1], bj = pj[1];  // {p.y, p.z, pn_xy, pn_z}
         const double pix = ai.w, piy = bi.x, piz = bi.y, pjx = aj.w, pjy = bj.x, pjz = bj.y;
         double e_xy, e_z;
-        pair_e(q0, q1, q2, bi.z, bj.z, bi.w, bj.w, pix, piy, piz, pjx, pjy, pjz, s2, e_xy, e_z);
+        ACL_FUSED_PAIR_E(q0, q1, q2, bi.z, bj.z, bi.w, bj.w, pix, piy, piz, pjx, pjy, pjz, s2, e_xy,
+                         e_z);
         bool gxy, gz;
         gate_decide_t<GM>(fcst(cst, FC_TXY), fcst(cst, FC_TZ), fcst(cst, FC_WIN), e_xy, e_z, q0,
                           q1, q2, bi.z, bj.z, bi.w, bj.w, pix, piy, piz, pjx, pjy, pjz, gxy, gz,
@@ -564,8 +585,8 @@ __device__ __forceinline__ void pair_gain_fused(KCtlParams* Pp, int b, int f,
         if (gxy) Fxy = fcst(cst, FC_K1XY) * (fcst(cst, FC_K2XY) * e_xy);
         if (gz) Fz = fcst(cst, FC_K1Z) * (fcst(cst, FC_K2Z) * e_z);
 #else
-        if (gxy) Fxy = fcst(cst, FC_K1XY) * ACL_GAIN_ATAN(fcst(cst, FC_K2XY) * e_xy, atab);
-        if (gz) Fz = fcst(cst, FC_K1Z) * ACL_GAIN_ATAN(fcst(cst, FC_K2Z) * e_z, atab);
+        if (gxy) Fxy = fcst(cst, FC_K1XY) * ACL_FUSED_ATAN(fcst(cst, FC_K2XY) * e_xy, atab);
+        if (gz) Fz = fcst(cst, FC_K1Z) * ACL_FUSED_ATAN(fcst(cst, FC_K2Z) * e_z, atab);
 #endif
       }
       const double f0 = Fxy * q0, f1 = Fxy * q1, f2 = Fz * q2;

@@ -345,6 +345,20 @@ class FleetLossyTrialArgs(ct.Structure):
     _fields_ = [("delay", FleetDelayTrialArgs), ("link", FleetLoss)]
 
 
+class GemmJobRec(ct.Structure):
+    """acl_internal_gemm_job_t (csrc/admm.hip, a test hook's record): GemmJob
+    (csrc/gemm_f64.h) field for field; pointers are device addresses."""
+    _fields_ = [(n, ct.c_void_p) for n in ("A", "B", "C", "D")] + [
+        (n, ct.c_int32) for n in ("m", "n", "k", "lda", "ldb", "ldc", "ldd")] + [
+        ("alpha", ct.c_double), ("beta", ct.c_double), ("skip", ct.c_void_p),
+        ("err2", ct.c_void_p), ("tnrm", ct.c_void_p), ("tdiag", ct.c_double),
+        ("tmask", ct.c_int32), ("trp", ct.c_void_p), ("nsp", ct.c_void_p),
+        ("nserr", ct.c_void_p), ("nsn", ct.c_int32), ("nscap", ct.c_double),
+        ("nstol", ct.c_double), ("gerr", ct.c_void_p), ("glo", ct.c_double),
+        ("ghi", ct.c_double), ("qB", ct.c_void_p), ("qlo", ct.c_double), ("qhi", ct.c_double),
+        ("qalpha", ct.c_double), ("qbeta", ct.c_double)]
+
+
 HUNG_BAD_INPUT = 0x01
 HUNG_NONFINITE = 0x02
 HUNG_CMP_INVALID = 0x04
@@ -511,6 +525,15 @@ def lib():
     if hasattr(L, "acl_internal_rsq_sweep"):  # (absent from older experiment builds)
         L.acl_internal_rsq_sweep.argtypes = [VP, VP, ct.c_int]
         L.acl_internal_rsq_sweep.restype = ct.c_int
+    if hasattr(L, "acl_internal_gemm_f64"):  # (absent from older experiment builds)
+        L.acl_internal_gemm_job_size.restype = ct.c_int
+        L.acl_internal_gemm_f64.argtypes = [ct.c_int, ct.c_int, ct.c_int, ct.c_int,
+                                            ct.POINTER(GemmJobRec), ct.c_int,
+                                            ct.POINTER(ct.c_int)]
+        L.acl_internal_gemm_f64.restype = ct.c_int
+    if hasattr(L, "acl_internal_fastmath_sweep"):  # (absent from older experiment builds)
+        L.acl_internal_fastmath_sweep.argtypes = [VP, VP, VP, ct.c_int]
+        L.acl_internal_fastmath_sweep.restype = ct.c_int
     if hasattr(L, "acl_internal_neighbourhoods"):  # (absent from older experiment builds)
         L.acl_internal_neighbourhoods.argtypes = [ct.c_int, ct.c_int, VP, VP, VP, ct.c_int]
         L.acl_internal_neighbourhoods.restype = ct.c_int

@@ -1348,19 +1348,13 @@ struct JobLists {
   int NP = 0;
   int njob[J_COUNT] = {};
   int mx[J_COUNT][2] = {};
-  // the kind's operands may be staged by LDS-DMA (gemm_f64.h): 16-byte
-  // aligned operands, even leading dimensions and sizes,
-  // 32-bit byte offsets (checked on the host over every job of the kind)
+  // the kind's operands may be staged by LDS-DMA: gemm_dma_eligible
+  // (gemm_f64.h), checked on the host over every job of the kind
   bool dma[J_COUNT] = {};
   void check_dma(const GemmJob* jobs) {
     for (int k = 0; k < J_COUNT; ++k) {
       bool ok = njob[k] > 0;
-      for (int i = 0; ok && i < njob[k]; ++i) {
-        const GemmJob& j = jobs[(size_t)k * NP + i];
-        const uintptr_t al = (uintptr_t)j.A | (uintptr_t)j.B | (uintptr_t)j.qB;
-        ok = (j.tmask & ~7) == 0 && (al & 15) == 0 && ((j.lda | j.ldb | j.m | j.k) & 1) == 0 &&
-             (long long)j.lda * j.k * 8 < (1ll << 30) && (long long)j.ldb * j.n * 8 < (1ll << 30);
-      }
+      for (int i = 0; ok && i < njob[k]; ++i) ok = gemm_dma_eligible(jobs[(size_t)k * NP + i]);
       dma[k] = ok;
     }
   }
@@ -1858,6 +1852,105 @@ extern "C" int acl_internal_psd_project(int nm, int N, const double* W, double e
   (void)hipFree(buf);
   (void)hipFree(sc);
   (void)hipFree(dp);
+  (void)hipFree(dj);
+  return rc;
+}
+
+// Test hook (not part of the public ABI; tests/test_gpu_gemm.py): one
+// gemm_f64 launch on caller-made descriptors. A record mirrors GemmJob field
+// for field (a flat POD without default member initialisers, so ctypes can
+// mirror it); every pointer in it is a device address.
+struct acl_internal_gemm_job_t {
+  const double* A;
+  const double* B;
+  const double* C;
+  double* D;
+  int32_t m, n, k;
+  int32_t lda, ldb, ldc, ldd;
+  double alpha, beta;
+  const int* skip;
+  double* err2;
+  const double* tnrm;
+  double tdiag;
+  int32_t tmask;
+  double* trp;
+  const double* nsp;
+  const double* nserr;
+  int32_t nsn;
+  double nscap, nstol;
+  const double* gerr;
+  double glo, ghi;
+  const double* qB;
+  double qlo, qhi, qalpha, qbeta;
+};
+
+// sizeof the record, for the Python mirror to check itself against
+extern "C" int acl_internal_gemm_job_size() { return (int)sizeof(acl_internal_gemm_job_t); }
+
+// staging 0: operands staged through registers; 1: as the ADMM host code
+// decides (LDS-DMA when the product is untransposed and every job passes
+// gemm_dma_eligible, JobLists::check_dma's rule; registers otherwise).
+// mmax / nmax are the maxima over the jobs, as JobLists takes them.
+// *dma_ran (host, may be NULL): 1 if the LDS-DMA kernel was launched.
+// Synchronous. Returns 0 on success, 1 for a descriptor it refuses (nothing
+// is launched: a negative dimension, a leading dimension smaller than its
+// rows, sym with m != n, nsp or qB without nserr, a missing pointer), 2 for a
+// HIP error. Default build (the four-wave 80 tile) only.
+extern "C" int acl_internal_gemm_f64(int ta, int tb, int sym, int staging,
+                                     const acl_internal_gemm_job_t* rec, int njobs,
+                                     int* dma_ran) {
+  using namespace acl_amd;
+  if (dma_ran) *dma_ran = 0;
+  if (gemm_tile() != 80 || !rec || njobs <= 0 || (staging != 0 && staging != 1)) return 1;
+  std::vector<GemmJob> jobs((size_t)njobs);
+  int mmax = 0, nmax = 0;
+  bool eligible = true;
+  for (int i = 0; i < njobs; ++i) {
+    const acl_internal_gemm_job_t& r = rec[i];
+    if (r.m < 0 || r.n < 0 || r.k < 0) return 1;
+    if (r.lda < std::max(1, ta ? r.k : r.m) || r.ldb < std::max(1, tb ? r.n : r.k) ||
+        r.ldd < std::max(1, r.m))
+      return 1;
+    const bool reads_c = r.beta != 0.0 || (r.qB && r.qbeta != 0.0);
+    if (reads_c && (!r.C || r.ldc < std::max(1, r.m))) return 1;
+    if (sym && r.m != r.n) return 1;
+    if ((r.nsp || r.qB) && !r.nserr) return 1;
+    if (r.nsp && r.nsn < 0) return 1;
+    if (r.tmask && !r.tnrm) return 1;
+    if (r.m > 0 && r.n > 0 && (!r.D || (r.k > 0 && (!r.A || !r.B)))) return 1;
+    GemmJob& j = jobs[i];
+    j.A = r.A; j.B = r.B; j.C = r.C; j.D = r.D;
+    j.m = r.m; j.n = r.n; j.k = r.k;
+    j.lda = r.lda; j.ldb = r.ldb; j.ldc = r.ldc; j.ldd = r.ldd;
+    j.alpha = r.alpha; j.beta = r.beta;
+    j.skip = r.skip; j.err2 = r.err2;
+    j.tnrm = r.tnrm; j.tdiag = r.tdiag; j.tmask = r.tmask;
+    j.trp = r.trp;
+    j.nsp = r.nsp; j.nserr = r.nserr; j.nsn = r.nsn; j.nscap = r.nscap; j.nstol = r.nstol;
+    j.gerr = r.gerr; j.glo = r.glo; j.ghi = r.ghi;
+    j.qB = r.qB; j.qlo = r.qlo; j.qhi = r.qhi; j.qalpha = r.qalpha; j.qbeta = r.qbeta;
+    mmax = std::max(mmax, j.m);
+    nmax = std::max(nmax, j.n);
+    eligible = eligible && gemm_dma_eligible(j);
+  }
+  // the LDS-DMA kernel only ever sees a job list that passes the rule
+  const bool dma = staging == 1 && !ta && !tb && eligible;
+  GemmJob* dj = nullptr;
+  if (hipMalloc((void**)&dj, jobs.size() * sizeof(GemmJob)) != hipSuccess) return 2;
+  int rc = 2;
+  do {
+    if (hipMemcpy(dj, jobs.data(), jobs.size() * sizeof(GemmJob), hipMemcpyHostToDevice) !=
+        hipSuccess)
+      break;
+    if (gemm_f64(ta != 0, tb != 0, dj, njobs, mmax, nmax, 0, nullptr, sym != 0, dma) !=
+        hipSuccess)
+      break;
+    if (hipDeviceSynchronize() != hipSuccess) break;
+    // (gemm_f64 launches nothing for an empty product; its DMA kernel is the
+    // untransposed default-tile one)
+    if (dma_ran) *dma_ran = (dma && ACL_GEMM_DMA && mmax > 0 && nmax > 0) ? 1 : 0;
+    rc = 0;
+  } while (0);
   (void)hipFree(dj);
   return rc;
 }

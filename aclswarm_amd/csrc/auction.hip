@@ -1726,6 +1726,33 @@ __global__ void rsq_sweep_kernel(const double* x, double* r, int m) {
   if (i < m) r[i] = __builtin_amdgcn_rsq(x[i]);
 }
 
+// test hook: the default build's control fast-math helpers, raw
+// (tests/test_gpu_fastmath.py). The table is staged in LDS as the callers
+// stage it. out is four planes of m: sqrt_nr1; its split form recombined (on
+// a copy of x the compiler cannot see through, so the two are computed
+// apart); acl_atan_b; acl_atan_b_vote, evaluated only where act[i] != 0 so
+// that its vote sees a partial exec mask (kFastmathInactive elsewhere).
+constexpr unsigned long long kFastmathInactive = 0x7ff8dead0000beefull;
+#if ACL_GAIN_FASTMATH
+__global__ void __launch_bounds__(256) fastmath_sweep_kernel(const double* x, const int* act,
+                                                             double* out, int m) {
+  __shared__ double atab[ACL_ATAB_N];
+  for (int k = threadIdx.x; k < ACL_ATAB_N; k += 256) atab[k] = ACL_ATAB_AT(k);
+  __syncthreads();
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= m) return;
+  const double xi = x[i];
+  out[i] = sqrt_nr1(xi);
+  double xc = xi;
+  asm volatile("" : "+v"(xc));
+  out[(size_t)m + i] = sqrt_nr1_edge(xc) ? xc : sqrt_nr1_step(xc);
+  out[2 * (size_t)m + i] = acl_atan_b(xi, atab);
+  double v = __longlong_as_double((long long)kFastmathInactive);
+  if (act[i]) v = acl_atan_b_vote(xi, atab);
+  out[3 * (size_t)m + i] = v;
+}
+#endif
+
 // the dynamic LDS of the auction kernel, fused or not
 static int auction_lds(int n, bool fuse) {
   const int a = make_alayout(n).total;
@@ -1791,6 +1818,19 @@ extern "C" int acl_internal_price_sweep(const double* x, float* fast, float* iee
   hipLaunchKernelGGL(acl_amd::price_sweep_kernel, dim3((m + 255) / 256), dim3(256), 0, 0, x, fast,
                      ieee, m);
   return hipDeviceSynchronize() == hipSuccess ? 0 : 1;
+}
+
+// x [m], act [m] (int32), out [4][m], all device; returns 0 on success, 1 for
+// a HIP error or a build without the fast-math helpers
+extern "C" int acl_internal_fastmath_sweep(const double* x, const int* act, double* out, int m) {
+  if (m <= 0) return 0;
+#if ACL_GAIN_FASTMATH
+  hipLaunchKernelGGL(acl_amd::fastmath_sweep_kernel, dim3((m + 255) / 256), dim3(256), 0, 0, x, act,
+                     out, m);
+  return hipDeviceSynchronize() == hipSuccess ? 0 : 1;
+#else
+  return 1;
+#endif
 }
 
 extern "C" int acl_internal_rsq_sweep(const double* x, double* r, int m) {

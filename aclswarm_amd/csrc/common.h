@@ -234,15 +234,18 @@ __device__ __forceinline__ double acl_atan_tab(double x, const double* tab) {
 }
 
 // Square root with one Goldschmidt step from v_rsq_f64 (relative error
-// ~2^-46): the distances of the control law's gated terms, where the parity
-// bar is 1e-5 relative on u. sqrt(negative) and NaN give NaN, +-0 and +inf
-// themselves, as std::sqrt.
+// ~2^-46: a start within e0 = 2^-23 leaves 1.5 e0^2 + 4 roundings = 2.2e-14;
+// 4.1e-15 measured over the normal range, tests/test_gpu_fastmath.py): the
+// distances of the control law's gated terms, where the parity bar is 1e-5
+// relative on u. sqrt(negative), -inf included, and NaN give NaN, +-0 and
+// +inf themselves, as std::sqrt. (Subnormal arguments are not needed here;
+// the hardware honours them, and the same test sees 5e-324 exact.)
 __device__ __forceinline__ double sqrt_nr1(double x) {
   const double y = __builtin_amdgcn_rsq(x);
   const double g = x * y, h = 0.5 * y;
   const double r = __builtin_fma(-g, h, 0.5);
   const double s = __builtin_fma(g, r, g);
-  return (x == 0.0 || __builtin_isinf(x)) ? x : s;
+  return (x == 0.0 || x == __builtin_inf()) ? x : s;  // (-inf: NaN, from the step)
 }
 
 // sqrt_nr1 in two parts, for a caller that votes once per wave on the
@@ -257,7 +260,7 @@ __device__ __forceinline__ double sqrt_nr1_step(double x) {
 }
 
 __device__ __forceinline__ bool sqrt_nr1_edge(double x) {
-  return x == 0.0 || __builtin_isinf(x);
+  return x == 0.0 || x == __builtin_inf();
 }
 
 // Rows k = 0..16 of {na, nb, da, db, a_k} for acl_atan_k32:

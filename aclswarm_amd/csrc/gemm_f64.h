@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include <hip/hip_runtime.h>
+#include <stdint.h>
 #include <stdlib.h>
 
 namespace acl_amd {
@@ -72,6 +73,19 @@ struct GemmJob {
   const double* qB = nullptr;
   double qlo = 0.0, qhi = 0.0, qalpha = 0.0, qbeta = 0.0;
 };
+
+// May this job's operands be staged by LDS-DMA (gemm80w4_f64_kernel<.., DMA>)?
+// A lane moves 16 bytes -- two rows of A at one k, two k of one column of B --
+// from a 32-bit byte offset: 16-byte aligned operands (qB too: the quintic
+// band reads it as B), even leading dimensions, even m and k, offsets below
+// 2^30, and no transform bit the kernel does not know. The host asks this of
+// every job of a launch (untransposed products only) before it passes
+// dma = true to gemm_f64.
+inline bool gemm_dma_eligible(const GemmJob& j) {
+  const uintptr_t al = (uintptr_t)j.A | (uintptr_t)j.B | (uintptr_t)j.qB;
+  return (j.tmask & ~7) == 0 && (al & 15) == 0 && ((j.lda | j.ldb | j.m | j.k) & 1) == 0 &&
+         (long long)j.lda * j.k * 8 < (1ll << 30) && (long long)j.ldb * j.n * 8 < (1ll << 30);
+}
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 

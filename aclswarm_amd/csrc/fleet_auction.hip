@@ -866,12 +866,6 @@ extern "C" size_t acl_fleet_delay_workspace_bytes(int32_t n, int32_t B, int32_t 
 
 namespace acl_amd {
 
-static acl_status_t fleet_error(const char* entry, const char* what) {
-  char msg[192];
-  snprintf(msg, sizeof msg, "%s: %s", entry, what);
-  return acl__set_error(msg);
-}
-
 // The argument checks the two entries share; *launch says whether anything
 // is left to do (B > 0). The workspace size is the entry's own check.
 static acl_status_t fleet_check(const char* entry, const acl_formations_t* F,

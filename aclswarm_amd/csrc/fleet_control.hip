@@ -474,9 +474,7 @@ __global__ void __launch_bounds__(kEcBlock) fleet_est_control_kernel(const EstCt
 }
 
 static acl_status_t ectl_error(const char* what) {
-  char msg[192];
-  snprintf(msg, sizeof msg, "acl_fleet_est_control_batch: %s", what);
-  return acl__set_error(msg);
+  return fleet_error("acl_fleet_est_control_batch", what);
 }
 
 }  // namespace acl_amd

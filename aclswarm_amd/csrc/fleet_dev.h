@@ -1,15 +1,30 @@
 // fleet_dev.h -- the fleet auction's workspace layout and table helpers,
-// shared by fleet_auction.hip (the kernel that owns them) and fleet_trial.hip
-// (whose commit kernel runs Auctioneer::setFormation on the same state).
+// shared by fleet_auction.hip (the kernel that owns them), fleet_trial.hip
+// (whose commit kernel runs Auctioneer::setFormation on the same state) and,
+// through fleet_loop_dev.h, the workspace layouts of both loops on the fleet
+// auction; and fleet_error, the argument-error message of every fleet entry
+// (fleet_auction, fleet_localize, fleet_control, fleet_episode, fleet_trial).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
+
+#include "../../include/aclswarm_amd.h"
+
+extern "C" acl_status_t acl__set_error(const char* msg);
 
 namespace acl_amd {
 
 constexpr int kFleetMaxN = 128;
+
+// "<entry>: <what>" as the thread's last error (acl__set_error copies it).
+inline acl_status_t fleet_error(const char* entry, const char* what) {
+  char msg[192];
+  snprintf(msg, sizeof msg, "%s: %s", entry, what);
+  return acl__set_error(msg);
+}
 
 // per-vehicle bookkeeping kept in the workspace between calls (all zero: a
 // freshly constructed auctioneer)

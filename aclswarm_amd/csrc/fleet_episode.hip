@@ -23,7 +23,13 @@
 //                         supervisor ring (episode_dev.h)
 // One workgroup per swarm in the two new kernels; both are O(n) .. O(n^2)
 // integer work per swarm and latency-bound: the step's time is the fleet
-// kernel's ticks and the control stage's gain stream.
+// kernel's ticks and the control stage's gain stream. What they do is shared
+// with the trials (fleet_trial.hip) and lives in fleet_loop_dev.h: the
+// commands, the stages of the hand-off, the workspace's common regions, the
+// tick arguments and the choice of the ticks' entry. This file keeps the two
+// kernels as calls to them, the episode's own checks (fidx, fidx_eff for a good
+// swarm, est.per_vehicle), the own-estimate tail of the workspace and the host
+// loop.
 //
 // A swarm whose fidx is out of range or that holds a row that is no
 // permutation at the start of the call is flagged once, by the call's first
@@ -51,7 +57,7 @@
 //                           against the true q
 #include "common.h"
 #include "episode_dev.h"
-#include "fleet_dev.h"  // kFleetMaxLat
+#include "fleet_loop_dev.h"
 
 #include "../../include/aclswarm_amd.h"
 
@@ -60,13 +66,11 @@ extern "C" acl_status_t acl__set_error(const char* msg);
 namespace acl_amd {
 
 constexpr int kFepMaxN = 128;
-constexpr int kFepBlock = 256;  // fleet_handoff_kernel: 4 waves, rows v = wave, wave + 4, ...
 
-// Workspace: the fleet kernel's own, then the control stage's hand-off
-// region (a WsLayout: pt, mode, rows, ...), its status and outputs, and the
-// loop's own small arrays.
-struct FepLayout {
-  size_t fleet, ctl, cst, u, us, ca, cmd, vf, fidx, skip, lst, ecs, total;
+// Workspace: the loops' common regions (fleet_loop_dev.h), then the
+// own-estimate entry's status arrays.
+struct FepLayout : FleetLoopLayout {
+  size_t lst, ecs, total;
 };
 
 // max_lat 0: acl_fleet_auction_batch's fleet part, else the delay layout's.
@@ -74,88 +78,34 @@ struct FepLayout {
 // own-estimate entry); nothing before them moves.
 inline FepLayout fep_layout(int n, int B, int cap, int max_lat = 0, bool own = false) {
   FepLayout L;
-  const size_t nb = (size_t)n, bb = (size_t)B;
-  size_t o = 0;
-  L.fleet = o;
-  o = ws_al(o + (max_lat ? acl_fleet_delay_workspace_bytes(n, B, cap, max_lat)
-                         : acl_fleet_workspace_bytes(n, B, cap)));
-  L.ctl = o;   o = ws_al(o + ws_layout(n, B).total);
-  L.cst = o;   o = ws_al(o + bb * sizeof(acl_swarm_status_t));
-  L.u = o;     o = ws_al(o + bb * nb * 3 * 8);
-  L.us = o;    o = ws_al(o + bb * nb * 3 * 8);
-  L.ca = o;    o = ws_al(o + bb * nb);
-  L.cmd = o;   o = ws_al(o + bb * nb);      // [B][n] u8: this auto-auction's commands
-  L.vf = o;    o = ws_al(o + bb * nb * 4);  // [B][n] i32: the ACL_FLEET_V_* of this step's ticks
-  L.fidx = o;  o = ws_al(o + bb * 4);       // [B] i32: fidx, -1 for a BAD_INPUT swarm
-  L.skip = o;  o = ws_al(o + bb);           // [B] u8: BAD_INPUT in this call
+  static_cast<FleetLoopLayout&>(L) = fleet_loop_layout(n, B, cap, fleet_log_len(max_lat));
+  size_t o = L.end;
   L.lst = o;
   L.ecs = o;
   if (own) {
-    o = ws_al(o + bb * sizeof(acl_fleet_localize_status_t));
+    o = ws_al(o + (size_t)B * sizeof(acl_fleet_localize_status_t));
     L.ecs = o;
-    o = ws_al(o + bb * sizeof(acl_fleet_control_status_t));
+    o = ws_al(o + (size_t)B * sizeof(acl_fleet_control_status_t));
   }
   L.total = o;
   return L;
 }
 
-struct FepArgs {
-  int n, B, F, step, k;
+struct FepArgs : FleetHandoff {
+  int F;
   const int32_t* fidx;
-  int32_t* fidx_eff;
-  uint8_t* skip;
-  const uint16_t* Pt;
   const uint8_t* open;
   const uint8_t* invalid;
   uint8_t* cmd;
-  int32_t* vf;
-  int32_t* vflags;
-  int32_t* vflags_hist;
-  int32_t* adopt_step;
-  const acl_fleet_status_t* status;
-  acl_fleet_episode_status_t* fst;
   acl_episode_status_t* est;
-  uint16_t* P;
-  uint16_t* ctlPt;
-  uint8_t* ctlMode;
-  uint16_t* ctlRows;
-  acl_swarm_status_t* cst;
-  const uint8_t* lat;  // [B][n][n] receiver-major; the delay entry only
-  int max_lat;
 };
 
-// CoordinationROS::autoauctionCb of every vehicle (coordination_ros.cpp:
-// 339-358) as the fleet kernel's commands, and the counts of what was asked.
+// Every vehicle's own autoauctionCb (fleet_auto_commands), on the auto-auction
+// steps.
 __global__ void __launch_bounds__(kFepMaxN) fleet_cmd_kernel(const FepArgs A) {
-  __shared__ int cnt_s[3];
-  const int b = (int)blockIdx.x, tid = (int)threadIdx.x, n = A.n;
+  const int b = (int)blockIdx.x;
   if (A.skip[b] != 0) return;  // block-uniform: the fleet kernel skips the swarm too
-  if (tid < 3) cnt_s[tid] = 0;
-  __syncthreads();
-  const size_t vb = (size_t)b * n;
-  int c = ACL_FLEET_NONE;
-  bool busy = false;
-  if (tid < n) {
-    c = A.invalid[vb + tid] != 0 ? ACL_FLEET_FLUSH : ACL_FLEET_START;
-    busy = A.open[vb + tid] != 0;
-    A.cmd[vb + tid] = (uint8_t)c;
-  }
-  const int ns = __popcll(__ballot(c == ACL_FLEET_START));
-  const int nr = __popcll(__ballot(c == ACL_FLEET_START && busy));
-  const int nf = __popcll(__ballot(c == ACL_FLEET_FLUSH));
-  if ((tid & 63) == 0) {
-    if (ns) atomicAdd(&cnt_s[0], ns);
-    if (nr) atomicAdd(&cnt_s[1], nr);
-    if (nf) atomicAdd(&cnt_s[2], nf);
-  }
-  __syncthreads();
-  if (tid == 0) {
-    acl_fleet_episode_status_t s = A.fst[b];
-    s.n_started += cnt_s[0];
-    s.n_restarted += cnt_s[1];
-    s.n_flushed += cnt_s[2];
-    A.fst[b] = s;
-  }
+  fleet_auto_commands(A.n, b, true, false, A.open, A.invalid, A.cmd, A.fst);
 }
 
 // kFirst (the call's first launch, before any tick): the swarm's input check
@@ -164,143 +114,26 @@ __global__ void __launch_bounds__(kFepMaxN) fleet_cmd_kernel(const FepArgs A) {
 // kLat (with kFirst, the delay entry): the swarm's latency matrix is part of
 // the input check.
 template <bool kFirst, bool kLat = false>
-__global__ void __launch_bounds__(kFepBlock) fleet_handoff_kernel(const FepArgs A) {
-  __shared__ int cnt_s[3];
+__global__ void __launch_bounds__(kFleetLoopBlock) fleet_handoff_kernel(const FepArgs A) {
   const int b = (int)blockIdx.x, tid = (int)threadIdx.x, n = A.n;
-  const int lane = tid & 63, wv = tid >> 6;
-  const size_t vb = (size_t)b * n;
-  const uint16_t* rows = A.Pt + vb * n;
   bool differs = false;  // some row is not row 0
   if (kFirst) {
     const int f = A.fidx[b];
-    bool bad = f < 0 || f >= A.F;
-    const unsigned long long lastmask = (n & 63) ? ((1ull << (n & 63)) - 1ull) : ~0ull;
-    const unsigned long long full0 = n > 64 ? ~0ull : lastmask;
-    const unsigned long long full1 = n > 64 ? lastmask : 0ull;
-    for (int v = wv; v < n; v += kFepBlock / 64) {
-      // a permutation <=> n entries below n that set n different bits
-      unsigned w0 = 0u, w1 = 0u, w2 = 0u, w3 = 0u;
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const int j = lane + 64 * s;
-        if (j < n) {
-          const unsigned x = rows[(size_t)v * n + j];
-          if (x >= (unsigned)n) bad = true;
-          else {
-            const unsigned bit = 1u << (x & 31);
-            const unsigned wd = x >> 5;
-            if (wd == 0) w0 |= bit;
-            else if (wd == 1) w1 |= bit;
-            else if (wd == 2) w2 |= bit;
-            else w3 |= bit;
-            if (x != rows[j]) differs = true;
-          }
-        }
-      }
-      w0 = wave_or_u32(w0);
-      w1 = wave_or_u32(w1);
-      w2 = wave_or_u32(w2);
-      w3 = wave_or_u32(w3);
-      if ((((unsigned long long)w1 << 32) | w0) != full0 ||
-          (((unsigned long long)w3 << 32) | w2) != full1)
-        bad = true;
-    }
-    if constexpr (kLat) {
-      // every off-diagonal entry in 1..max_lat, as the fleet kernel requires
-      const uint8_t* latb = A.lat + vb * n;
-      for (int k = tid; k < n * n; k += kFepBlock) {
-        const int w = k / n, l = latb[k];
-        if (k - w * n != w && (l < 1 || l > A.max_lat)) bad = true;
-      }
-    }
-    bad = __syncthreads_or(bad) != 0;
-    if (tid == 0) {
-      A.fidx_eff[b] = bad ? -1 : f;
-      A.skip[b] = bad ? 1 : 0;
-      A.fst[b].flags = (A.fst[b].flags & ACL_FLEET_OVERFLOW) | (bad ? ACL_FLEET_BAD_INPUT : 0);
-      if (bad) {
-        acl_swarm_status_t st = {};
-        st.flags = ACL_SWARM_BAD_INPUT;  // the control kernels leave the swarm alone
-        A.cst[b] = st;
-      }
-    }
-    if (bad) return;
+    const bool bad = fleet_input_check<kLat>(A, b, f < 0 || f >= A.F, differs);
+    fleet_input_mark(A, b, bad);
+    if (bad) return;  // block-uniform
+    if (tid == 0) A.fidx_eff[b] = f;
   } else {
     if (A.skip[b] != 0) {  // block-uniform
       if (A.vflags_hist && tid < n) A.vflags_hist[((size_t)A.k * A.B + b) * n + tid] = 0;
       return;
     }
-    if (tid < 3) cnt_s[tid] = 0;
-    __syncthreads();
-    int x = 0;
-    if (tid < n) {
-      x = A.vf[vb + tid];
-      if (x) {
-        A.vflags[vb + tid] |= x;
-        A.vf[vb + tid] = 0;
-        if (x & ACL_FLEET_V_ADOPTED) A.adopt_step[vb + tid] = A.step;
-      }
-      if (A.vflags_hist) A.vflags_hist[((size_t)A.k * A.B + b) * n + tid] = x;
-    }
-    const int nc = __popcll(__ballot((x & ACL_FLEET_V_CONSENSUS) != 0));
-    const int na = __popcll(__ballot((x & ACL_FLEET_V_ADOPTED) != 0));
-    const int ni = __popcll(__ballot((x & ACL_FLEET_V_INVALID) != 0));
-    if (lane == 0) {
-      if (nc) atomicAdd(&cnt_s[0], nc);
-      if (na) atomicAdd(&cnt_s[1], na);
-      if (ni) atomicAdd(&cnt_s[2], ni);
-    }
-    __syncthreads();
-    const int adopted = cnt_s[1];
-    if (tid == 0) {
-      const acl_fleet_status_t fs = A.status[b];
-      acl_fleet_episode_status_t s = A.fst[b];
-      s.ticks_run += fs.ticks_run;
-      s.flags |= fs.flags & ACL_FLEET_OVERFLOW;
-      s.n_consensus += cnt_s[0];
-      s.n_adopted += adopted;
-      s.n_invalid += cnt_s[2];
-      A.fst[b] = s;
-    }
-    if (adopted == 0) return;  // the tables the vehicles fly are unchanged
-    // are the n rows one table? every entry against row 0's, a wave per row
-    for (int v = wv; v < n; v += kFepBlock / 64) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const int j = lane + 64 * s;
-        if (j < n && rows[(size_t)v * n + j] != rows[j]) differs = true;
-      }
-    }
+    int x;
+    if (fleet_step_flags(A, b, x) == 0) return;  // the tables the vehicles fly are unchanged
+    differs = fleet_rows_differ(A, b);
   }
-  const bool mixed = __syncthreads_or(__any(differs)) != 0;
-  // the control hand-off, in adopt_kernel's layouts (episode.hip). The rows
-  // are permutations: checked at the start of the call, and the fleet kernel
-  // adopts valid tables only.
-  if (!mixed) {
-    for (int j = tid; j < n; j += kFepBlock) {
-      const uint16_t v = rows[j];
-      A.ctlPt[vb + j] = v;
-      A.P[vb + v] = (uint16_t)j;
-    }
-  } else {
-    uint16_t* crows = A.ctlRows + vb * n;
-    for (int v = wv; v < n; v += kFepBlock / 64) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const int j = lane + 64 * s;
-        if (j < n) {
-          const uint16_t x = rows[(size_t)v * n + j];
-          crows[(size_t)v * n + j] = x;
-          if ((int)x == v) A.P[vb + v] = (uint16_t)j;  // the vehicle's point in its own row
-        }
-      }
-    }
-  }
-  if (tid == 0) {
-    A.ctlMode[b] = mixed ? 1 : 0;
-    A.est[b].per_vehicle = mixed ? 1 : 0;
-    A.cst[b] = acl_swarm_status_t{};
-  }
+  const bool mixed = fleet_handoff_write(A, b, differs);
+  if (tid == 0) A.est[b].per_vehicle = mixed ? 1 : 0;
 }
 
 // The own-estimate entry's arguments beside acl_fleet_lossy_episode_args_t.
@@ -352,11 +185,11 @@ __device__ __forceinline__ double wave_max_gt(double m) {
 // (A template, first used below the host loop, so that hipcc emits it after the
 // file's existing kernels and their assembly stays what it was.)
 template <bool kDiag>
-__global__ void __launch_bounds__(kFepBlock) fleet_est_err_kernel(const EstErrArgs A) {
+__global__ void __launch_bounds__(kFleetLoopBlock) fleet_est_err_kernel(const EstErrArgs A) {
   __shared__ double q_s[3 * kFepMaxN];
   __shared__ unsigned long long adj_s[2 * kFepMaxN];
-  __shared__ double d2_s[kFepBlock / 64][kFepMaxN];
-  __shared__ double red_s[kFepBlock / 64][3];
+  __shared__ double d2_s[kFleetLoopBlock / 64][kFepMaxN];
+  __shared__ double red_s[kFleetLoopBlock / 64][3];
   const int b = (int)blockIdx.x, tid = (int)threadIdx.x, n = A.n;
   if (A.skip[b] != 0) return;  // block-uniform
   if (A.round != 0 && tid == 0) {
@@ -372,13 +205,13 @@ __global__ void __launch_bounds__(kFepBlock) fleet_est_err_kernel(const EstErrAr
   const size_t vb = (size_t)b * n;
   {
     const double* gq = A.q + vb * 3;
-    for (int k = tid; k < 3 * n; k += kFepBlock) q_s[k] = gq[k];
+    for (int k = tid; k < 3 * n; k += kFleetLoopBlock) q_s[k] = gq[k];
     const uint64_t* ga = A.adj + (size_t)A.fidx_eff[b] * n * NW;  // (not skipped: fidx is valid)
-    for (int k = tid; k < n * NW; k += kFepBlock) adj_s[k] = ga[k];
+    for (int k = tid; k < n * NW; k += kFleetLoopBlock) adj_s[k] = ga[k];
   }
   __syncthreads();
   double m_own = 0.0, m_nbr = 0.0, m_all = 0.0;
-  for (int v0 = 0; v0 < n; v0 += kFepBlock / 64) {  // block-uniform trip count
+  for (int v0 = 0; v0 < n; v0 += kFleetLoopBlock / 64) {  // block-uniform trip count
     const int v = v0 + wv;
     const bool act = v < n;
     unsigned x[2] = {0xFFFFu, 0xFFFFu};
@@ -436,7 +269,7 @@ __global__ void __launch_bounds__(kFepBlock) fleet_est_err_kernel(const EstErrAr
   __syncthreads();
   if (tid < 3) {
     double m = red_s[0][tid];
-    for (int w = 1; w < kFepBlock / 64; ++w)
+    for (int w = 1; w < kFleetLoopBlock / 64; ++w)
       if (red_s[w][tid] > m) m = red_s[w][tid];
     if (A.err2_hist) A.err2_hist[((size_t)A.k * A.B + b) * 3 + tid] = m;
     double* acc = &A.xst[b].err2_own + tid;
@@ -483,11 +316,7 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
                      const acl_fleet_loss_t* link, void* stream,
                      const acl_amd::FepOwn* own = nullptr) {
   using namespace acl_amd;
-  static char msg[200];
-  auto fail = [&](const char* what) {
-    snprintf(msg, sizeof(msg), "%s: %s", who, what);
-    return acl__set_error(msg);
-  };
+  auto fail = [&](const char* what) { return fleet_error(who, what); };
   if (!F || !a) return fail("null argument");
   const int n = F->n, B = a->B;
   if (n < 1 || n > kFepMaxN) return fail("n out of range [1, 128]");
@@ -546,22 +375,8 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
   A.cst = reinterpret_cast<acl_swarm_status_t*>(ws + W.cst);
   A.lat = lat; A.max_lat = max_lat;
 
-  // the ticks: the fleet kernel on the episode's state; its vflags are the
-  // step's own (A.vf, cleared by the hand-off), the caller's stay sticky
-  acl_fleet_lossy_args_t fl = {};
-  if (link) fl.link = *link;
-  acl_fleet_delay_args_t& fd = fl.delay;
-  fd.lat = lat; fd.max_lat = max_lat;
-  acl_fleet_auction_args_t& fa = fd.base;
-  fa.B = B; fa.ticks = a->ticks_per_step; fa.max_iter = a->max_iter; fa.queue_cap = a->queue_cap;
-  fa.fidx = fidx_eff; fa.q = a->q; fa.Pt = a->Pt; fa.open = a->open; fa.invalid = a->invalid;
-  fa.just_received = a->just_received; fa.biditer = a->biditer; fa.price = a->price;
-  fa.who = a->who; fa.Rt = a->Rt; fa.final_price = a->final_price; fa.final_who = a->final_who;
-  fa.done_tick = a->done_tick; fa.vflags = A.vf; fa.n_thrown = a->n_thrown;
-  fa.n_tally = a->n_tally; fa.queue_len = a->queue_len; fa.status = a->status;
-  fa.workspace = ws + W.fleet;
-  fa.workspace_bytes = delay ? acl_fleet_delay_workspace_bytes(n, B, a->queue_cap, max_lat)
-                             : acl_fleet_workspace_bytes(n, B, a->queue_cap);
+  // the ticks: the fleet kernel on the episode's state
+  acl_fleet_lossy_args_t fl = fleet_tick_args(a, n, W, lat, max_lat, link);
 
   acl_control_args_t cs = {};
   cs.B = B; cs.fidx = fidx_eff; cs.q = a->q; cs.vel = a->vel; cs.P = a->P;
@@ -570,7 +385,6 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
 
   // the loop on own estimates: the three public entries' arguments
   acl_fleet_localize_args_t lo = {};
-  acl_fleet_est_args_t ea = {};
   acl_fleet_est_control_args_t ec = {};
   EstErrArgs X = {};
   if (own) {
@@ -579,7 +393,6 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
     lo.B = B; lo.rounds = 1; lo.q_rounds = 1; lo.fidx = fidx_eff; lo.Pt = a->Pt; lo.q = a->q;
     lo.stamp = own->loc_stamp; lo.est = own->loc_est; lo.round = own->loc_round;
     lo.loss = link->loss; lo.seed = link->seed; lo.n_lost = own->loc_n_lost; lo.status = lst;
-    ea.est = own->loc_est;
     ec.B = B; ec.fidx = fidx_eff; ec.est = own->loc_est; ec.vel = a->vel; ec.Pt = a->Pt;
     ec.u = u; ec.u_safe = us; ec.ca_flag = ca;
     ec.status = reinterpret_cast<acl_fleet_control_status_t*>(ws + W.ecs);
@@ -607,9 +420,9 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
   }
   // the call's input check and its hand-off from the rows alone
   if (delay)
-    hipLaunchKernelGGL((fleet_handoff_kernel<true, true>), dim3(B), dim3(kFepBlock), 0, s, A);
+    hipLaunchKernelGGL((fleet_handoff_kernel<true, true>), dim3(B), dim3(kFleetLoopBlock), 0, s, A);
   else
-    hipLaunchKernelGGL(fleet_handoff_kernel<true>, dim3(B), dim3(kFepBlock), 0, s, A);
+    hipLaunchKernelGGL(fleet_handoff_kernel<true>, dim3(B), dim3(kFleetLoopBlock), 0, s, A);
   if (hipGetLastError() != hipSuccess)
     return acl__set_error("fleet_handoff_kernel launch failed");
   for (int k = 0; k < a->steps; ++k) {
@@ -628,18 +441,10 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
       if (hipGetLastError() != hipSuccess)
         return acl__set_error("fleet_cmd_kernel launch failed");
     }
-    fa.cmd = auction ? cmd : nullptr;
-    acl_status_t r;
-    if (own) {
-      ea.lossy = fl;
-      r = acl_fleet_est_auction_batch(F, &ea, stream);
-    } else {
-      r = link    ? acl_fleet_lossy_auction_batch(F, &fl, stream)
-          : delay ? acl_fleet_delay_auction_batch(F, &fd, stream)
-                  : acl_fleet_auction_batch(F, &fa, stream);
-    }
+    fl.delay.base.cmd = auction ? cmd : nullptr;
+    acl_status_t r = fleet_run_ticks(F, fl, link != nullptr, own ? own->loc_est : nullptr, stream);
     if (r != ACL_OK) return r;
-    hipLaunchKernelGGL(fleet_handoff_kernel<false>, dim3(B), dim3(kFepBlock), 0, s, A);
+    hipLaunchKernelGGL(fleet_handoff_kernel<false>, dim3(B), dim3(kFleetLoopBlock), 0, s, A);
     if (hipGetLastError() != hipSuccess)
       return acl__set_error("fleet_handoff_kernel launch failed");
     r = own ? acl_fleet_est_control_batch(F, &ec, stream) : run_control(F, &cs, s, CTL_MIXED);
@@ -662,7 +467,7 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
 acl_status_t est_err_launch(const acl_amd::EstErrArgs& X, bool diag, hipStream_t s) {
   using namespace acl_amd;
   if (diag)
-    hipLaunchKernelGGL(fleet_est_err_kernel<true>, dim3(X.B), dim3(kFepBlock), 0, s, X);
+    hipLaunchKernelGGL(fleet_est_err_kernel<true>, dim3(X.B), dim3(kFleetLoopBlock), 0, s, X);
   else
     hipLaunchKernelGGL(fleet_est_err_kernel<false>, dim3(X.B), dim3(64), 0, s, X);
   if (hipGetLastError() != hipSuccess) return acl__set_error("fleet_est_err_kernel launch failed");

@@ -302,9 +302,7 @@ __global__ void __launch_bounds__(64 * LocWaves<S>::value) fleet_localize_kernel
 }
 
 static acl_status_t loc_error(const char* what) {
-  char msg[192];
-  snprintf(msg, sizeof msg, "acl_fleet_localize_batch: %s", what);
-  return acl__set_error(msg);
+  return fleet_error("acl_fleet_localize_batch", what);
 }
 
 template <bool Lo>

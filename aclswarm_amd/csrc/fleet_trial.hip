@@ -32,7 +32,11 @@
 //   trial_tick_kernel<true>     every sample_every steps, one supervisor tick
 // The hand-off is one kernel of its own rather than fleet_episode.hip's
 // followed by a per-swarm one: one launch per step instead of two, and the
-// controller starts need the same per-vehicle flags the counters read.
+// controller starts need the same per-vehicle flags the counters read. Its
+// stages, the commands, the workspace's common regions and the tick arguments
+// are the episodes' too and live in fleet_loop_dev.h; what a trial does beyond
+// an episode stays here: the commit, the countdown, ctl_on, vehicle 0's
+// assignment message, the skip of a finished trial, zstep.
 // One workgroup per swarm in the new kernels; all are O(n) .. O(n^2) integer
 // work per swarm and latency-bound.
 //
@@ -47,7 +51,7 @@
 //
 // Compiled with -ffp-contract=off (trial_dev.h).
 #include "common.h"
-#include "fleet_dev.h"
+#include "fleet_loop_dev.h"
 #include "trial_dev.h"
 
 #include "../../include/aclswarm_amd.h"
@@ -56,49 +60,30 @@ extern "C" acl_status_t acl__set_error(const char* msg);
 
 namespace acl_amd {
 
-constexpr int kFtrBlock = 256;  // 4 waves; vehicle v = wave, wave + 4, ... where a wave works per vehicle
-
-// Workspace: the fleet kernel's own, then the control stage's hand-off
-// region (a WsLayout: pt, mode, rows, ...), its status and outputs, and the
-// loop's own small arrays.
-struct FtrLayout {
-  size_t fleet, ctl, cst, u, us, ca, cmd, vf, fidx, skip, zstep, total;
+// Workspace: the loops' common regions (fleet_loop_dev.h), then the trial's own.
+struct FtrLayout : FleetLoopLayout {
+  size_t zstep, total;
 };
 
 // R 0: acl_fleet_auction_batch's fleet part, else the delay layout's with
 // publication logs of R entries
 inline FtrLayout ftr_layout(int n, int B, int cap, int R = 0) {
   FtrLayout L;
-  const size_t nb = (size_t)n, bb = (size_t)B;
-  size_t o = 0;
-  L.fleet = o; o = ws_al(o + (size_t)B * fleet_layout(n, cap, R).total);
-  L.ctl = o;   o = ws_al(o + ws_layout(n, B).total);
-  L.cst = o;   o = ws_al(o + bb * sizeof(acl_swarm_status_t));
-  L.u = o;     o = ws_al(o + bb * nb * 3 * 8);
-  L.us = o;    o = ws_al(o + bb * nb * 3 * 8);
-  L.ca = o;    o = ws_al(o + bb * nb);
-  L.cmd = o;   o = ws_al(o + bb * nb);      // [B][n] u8: this step's commands
-  L.vf = o;    o = ws_al(o + bb * nb * 4);  // [B][n] i32: the ACL_FLEET_V_* of this step's ticks
-  L.fidx = o;  o = ws_al(o + bb * 4);       // [B] i32: fidx, -1 for a finished or BAD_INPUT swarm
-  L.skip = o;  o = ws_al(o + bb);           // [B] u8: BAD_INPUT in this call
-  L.zstep = o; o = ws_al(o + bb);           // [B] u8: the swarm commits a formation this step
-  L.total = o;
+  static_cast<FleetLoopLayout&>(L) = fleet_loop_layout(n, B, cap, R);
+  L.zstep = L.end;  // [B] u8: the swarm commits a formation this step
+  L.total = ws_al(L.zstep + (size_t)B);
   return L;
 }
 
-struct FtrArgs {
-  int n, B, K, F, step, k, cap;
+struct FtrArgs : FleetHandoff {
+  int K, F, cap;
   int settle_steps, auction_every;
   const int32_t* fseq;
   int32_t* fidx;
-  int32_t* fidx_eff;
-  uint8_t* skip;
   uint8_t* zstep;
   acl_trial_status_t* ts;
-  uint16_t* P;
   uint8_t* ctl_on;
   int32_t* n_assign;
-  uint16_t* Pt;
   uint8_t* open;
   uint8_t* invalid;
   uint8_t* just_received;
@@ -106,19 +91,7 @@ struct FtrArgs {
   float* price;
   int32_t* who;
   uint8_t* cmd;
-  int32_t* vf;
-  int32_t* vflags;
-  int32_t* vflags_hist;
-  int32_t* adopt_step;
-  const acl_fleet_status_t* status;
-  acl_fleet_episode_status_t* fst;
-  uint16_t* ctlPt;
-  uint8_t* ctlMode;
-  uint16_t* ctlRows;
-  acl_swarm_status_t* cst;
   unsigned char* fleet_ws;
-  const uint8_t* lat;  // [B][n][n] receiver-major; the delay entries only
-  int max_lat;         // (0 otherwise)
 };
 
 // the arrays acl_fleet_trial_init alone writes
@@ -135,13 +108,13 @@ struct FtrInit {
 
 // ---- the start of a trial (acl_fleet_trial_init) ------------------------------
 // trial_init_kernel's state (trial.hip) and freshly constructed auctioneers.
-__global__ void __launch_bounds__(kFtrBlock) fleet_trial_init_kernel(const TrialDev D,
+__global__ void __launch_bounds__(kFleetLoopBlock) fleet_trial_init_kernel(const TrialDev D,
                                                                      const FtrArgs A,
                                                                      const FtrInit I) {
   const int b = blockIdx.x, tid = threadIdx.x, n = D.n, K = D.K;
   const size_t bn = (size_t)b * n;
   const int L = D.tp.ep.bufflen;
-  for (int v = tid; v < n; v += kFtrBlock) {
+  for (int v = tid; v < n; v += kFleetLoopBlock) {
     D.P[bn + v] = (uint16_t)v;  // before any formation: the identity (setFormation)
     D.ctlPt[bn + v] = (uint16_t)v;
     D.ctl_on[bn + v] = 0;
@@ -161,7 +134,7 @@ __global__ void __launch_bounds__(kFtrBlock) fleet_trial_init_kernel(const Trial
     I.queue_len[bn + v] = 0;
     for (int a = 0; a < 6; ++a) I.Rt[(bn + v) * 6 + a] = 0.0;
   }
-  for (size_t k = tid; k < (size_t)n * n; k += kFtrBlock) {
+  for (size_t k = tid; k < (size_t)n * n; k += kFleetLoopBlock) {
     const size_t i = bn * n + k;
     A.Pt[i] = (uint16_t)(k % n);
     A.price[i] = 0.0f;
@@ -169,12 +142,12 @@ __global__ void __launch_bounds__(kFtrBlock) fleet_trial_init_kernel(const Trial
     I.final_price[i] = 0.0f;
     I.final_who[i] = 0;
   }
-  for (int k = tid; k < K; k += kFtrBlock) {
+  for (int k = tid; k < K; k += kFleetLoopBlock) {
     D.t_conv[(size_t)b * K + k] = 0.0;
     D.t_avoid[(size_t)b * K + k] = 0.0;
     D.n_assign[(size_t)b * K + k] = 0;
   }
-  for (size_t k = tid; k < (size_t)L * n; k += kFtrBlock) {
+  for (size_t k = tid; k < (size_t)L * n; k += kFleetLoopBlock) {
     D.ring_u[(size_t)b * L * n + k] = 0.0;
     D.ring_ca[(size_t)b * L * n + k] = 0;
   }
@@ -201,8 +174,7 @@ __global__ void __launch_bounds__(kFtrBlock) fleet_trial_init_kernel(const Trial
 // as in the fleet kernel; a thread per vehicle for the commands.
 // kDelay: the fleet workspace is the delay layout (acl_fleet_delay_trial_batch).
 template <bool kDelay>
-__global__ void __launch_bounds__(kFtrBlock) fleet_trial_pre_kernel(const FtrArgs A) {
-  __shared__ int cnt_s[3];
+__global__ void __launch_bounds__(kFleetLoopBlock) fleet_trial_pre_kernel(const FtrArgs A) {
   const int b = (int)blockIdx.x, tid = (int)threadIdx.x, n = A.n;
   const int lane = tid & 63, wv = tid >> 6;
   if (A.skip[b] != 0) return;  // block-uniform: BAD_INPUT in this call, nothing is written
@@ -244,7 +216,7 @@ __global__ void __launch_bounds__(kFtrBlock) fleet_trial_pre_kernel(const FtrArg
   }
   const bool done = t.done_step >= 0;
   if (zs) {
-    for (int v = tid; v < n; v += kFtrBlock) {
+    for (int v = tid; v < n; v += kFleetLoopBlock) {
       A.P[vb + v] = (uint16_t)v;
       A.ctlPt[vb + v] = (uint16_t)v;
       A.ctl_on[vb + v] = 0;
@@ -260,89 +232,49 @@ __global__ void __launch_bounds__(kFtrBlock) fleet_trial_pre_kernel(const FtrArg
     const FleetLayout L = fleet_layout(n, A.cap, kDelay ? fleet_log_len(A.max_lat) : 0);
     unsigned char* ws = A.fleet_ws + (size_t)b * L.total;
     FleetMeta* meta_g = reinterpret_cast<FleetMeta*>(ws + L.meta);
-    float* stale_g = reinterpret_cast<float*>(ws + L.stale);
-    const size_t tw = 2 * (size_t)n;  // a table in 4-byte words
-    for (int v = wv; v < n; v += kFtrBlock / 64) {
+    for (int v = wv; v < n; v += kFleetLoopBlock / 64) {
       float* pr = A.price + (vb + v) * n;
       int32_t* wh = A.who + (vb + v) * n;
-      if constexpr (kDelay) {
-        // only the bucket masks of the vehicle's bookkeeping change
-        fleet_clear_table<2>(pr, wh, n, lane);
-        uint16_t* row = A.Pt + (vb + v) * n;
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          const int j = lane + 64 * s;
-          if (j < n) row[j] = (uint16_t)j;
+      FleetMeta* mg = meta_g + v;
+      if constexpr (!kDelay) {
+        const int live = mg->live, live_iter = mg->live_iter;
+        if (live) {
+          // the bid in flight outlives the table it was read from, as at a START
+          // or FLUSH command. The stale slot is free: every step runs at least
+          // one tick after its commands, tick 0 delivers everything in flight
+          // and processing clears both in-flight marks of every vehicle, so a
+          // stale bid never survives the step that made it.
+          float* sp = reinterpret_cast<float*>(ws + L.stale) + (size_t)v * 2 * n;
+          fleet_copy_table<2>(sp, reinterpret_cast<int32_t*>(sp + n), pr, wh, n, lane);
+          if (lane == 0) {
+            mg->stale = 1;
+            mg->stale_iter = live_iter;
+            mg->live = 0;
+          }
         }
-        if (lane == 0) {
-          FleetMeta* mg = meta_g + v;
-          mg->mc[0] = mg->mc[1] = mg->mn[0] = mg->mn[1] = 0ull;
-          A.open[vb + v] = 0;
-          A.biditer[vb + v] = 0;
-          A.just_received[vb + v] = 1;
-        }
-        continue;
       }
-      FleetMeta m = meta_g[v];
-      if (m.live) {
-        // the bid in flight outlives the table it was read from, as at a START
-        // or FLUSH command. The stale slot is free: every step runs at least
-        // one tick after its commands, tick 0 delivers everything in flight
-        // and processing clears both in-flight marks of every vehicle, so a
-        // stale bid never survives the step that made it.
-        float* sp = stale_g + (size_t)v * tw;
-        fleet_copy_table<2>(sp, reinterpret_cast<int32_t*>(sp + n), pr, wh, n, lane);
-        m.stale = 1;
-        m.stale_iter = m.live_iter;
-        m.live = 0;
-      }
-      fleet_clear_table<2>(pr, wh, n, lane);  // (after the copy: the same lane owns entry j in both)
+      // (after the copy: the same lane owns entry j in both)
+      fleet_clear_table<2>(pr, wh, n, lane);
       uint16_t* row = A.Pt + (vb + v) * n;
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         const int j = lane + 64 * s;
         if (j < n) row[j] = (uint16_t)j;
       }
-      m.mc[0] = m.mc[1] = m.mn[0] = m.mn[1] = 0ull;
       if (lane == 0) {
-        meta_g[v] = m;
+        // (of the vehicle's bookkeeping only the bucket masks change)
+        mg->mc[0] = mg->mc[1] = mg->mn[0] = mg->mn[1] = 0ull;
         A.open[vb + v] = 0;
         A.biditer[vb + v] = 0;
         A.just_received[vb + v] = 1;
       }
     }
   }
-  // every vehicle's autoauctionCb (coordination_ros.cpp:339-358) as the fleet
-  // kernel's commands, and the counts of what was asked
-  if (tid < 3) cnt_s[tid] = 0;
-  __syncthreads();
-  int c = ACL_FLEET_NONE;
-  bool busy = false;
-  if (tid < n) {
-    if (now) {
-      c = A.invalid[vb + tid] != 0 ? ACL_FLEET_FLUSH : ACL_FLEET_START;
-      busy = zs == 0 && A.open[vb + tid] != 0;  // (a commit has just closed every auctioneer)
-    }
-    A.cmd[vb + tid] = (uint8_t)c;
-  }
-  const int ns = __popcll(__ballot(c == ACL_FLEET_START));
-  const int nr = __popcll(__ballot(c == ACL_FLEET_START && busy));
-  const int nf = __popcll(__ballot(c == ACL_FLEET_FLUSH));
-  if (lane == 0) {
-    if (ns) atomicAdd(&cnt_s[0], ns);
-    if (nr) atomicAdd(&cnt_s[1], nr);
-    if (nf) atomicAdd(&cnt_s[2], nf);
-  }
-  __syncthreads();
+  // every vehicle's autoauctionCb when the countdown fires (a commit has just
+  // closed every auctioneer)
+  fleet_auto_commands(n, b, now, zs != 0, A.open, A.invalid, A.cmd, A.fst);
   if (tid == 0) {
-    if (now) {
-      acl_fleet_episode_status_t s = A.fst[b];
-      s.n_started += cnt_s[0];
-      s.n_restarted += cnt_s[1];
-      s.n_flushed += cnt_s[2];
-      A.fst[b] = s;
-      ++t.n_auctions;
-    }
+    if (now) ++t.n_auctions;
     if (fbad) A.fidx[b] = 0;
     if (zs) {
       A.fidx[b] = f;
@@ -369,109 +301,24 @@ __global__ void __launch_bounds__(kFtrBlock) fleet_trial_pre_kernel(const FtrArg
 // kLat (with kFirst, the delay entry): the swarm's latency matrix is part of
 // the input check.
 template <bool kFirst, bool kLat = false>
-__global__ void __launch_bounds__(kFtrBlock) fleet_trial_handoff_kernel(const FtrArgs A) {
-  __shared__ int cnt_s[3];
-  __shared__ int adopt0_s;
+__global__ void __launch_bounds__(kFleetLoopBlock) fleet_trial_handoff_kernel(const FtrArgs A) {
   const int b = (int)blockIdx.x, tid = (int)threadIdx.x, n = A.n;
-  const int lane = tid & 63, wv = tid >> 6;
-  const size_t vb = (size_t)b * n;
-  const uint16_t* rows = A.Pt + vb * n;
   bool differs = false;  // some row is not row 0
   if (kFirst) {
-    bool bad = false;
-    const unsigned long long lastmask = (n & 63) ? ((1ull << (n & 63)) - 1ull) : ~0ull;
-    const unsigned long long full0 = n > 64 ? ~0ull : lastmask;
-    const unsigned long long full1 = n > 64 ? lastmask : 0ull;
-    for (int v = wv; v < n; v += kFtrBlock / 64) {
-      // a permutation <=> n entries below n that set n different bits
-      unsigned w0 = 0u, w1 = 0u, w2 = 0u, w3 = 0u;
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const int j = lane + 64 * s;
-        if (j < n) {
-          const unsigned x = rows[(size_t)v * n + j];
-          if (x >= (unsigned)n) bad = true;
-          else {
-            const unsigned bit = 1u << (x & 31);
-            const unsigned wd = x >> 5;
-            if (wd == 0) w0 |= bit;
-            else if (wd == 1) w1 |= bit;
-            else if (wd == 2) w2 |= bit;
-            else w3 |= bit;
-            if (x != rows[j]) differs = true;
-          }
-        }
-      }
-      w0 = wave_or_u32(w0);
-      w1 = wave_or_u32(w1);
-      w2 = wave_or_u32(w2);
-      w3 = wave_or_u32(w3);
-      if ((((unsigned long long)w1 << 32) | w0) != full0 ||
-          (((unsigned long long)w3 << 32) | w2) != full1)
-        bad = true;
-    }
-    if constexpr (kLat) {
-      // every off-diagonal entry in 1..max_lat, as the fleet kernel requires
-      const uint8_t* latb = A.lat + vb * n;
-      for (int k = tid; k < n * n; k += kFtrBlock) {
-        const int w = k / n, l = latb[k];
-        if (k - w * n != w && (l < 1 || l > A.max_lat)) bad = true;
-      }
-    }
-    bad = __syncthreads_or(bad) != 0;
-    if (tid == 0) {
-      A.skip[b] = bad ? 1 : 0;
-      A.fst[b].flags = (A.fst[b].flags & ACL_FLEET_OVERFLOW) | (bad ? ACL_FLEET_BAD_INPUT : 0);
-      if (bad) {
-        A.fidx_eff[b] = -1;  // (the pre kernel, which writes it otherwise, skips the swarm)
-        acl_swarm_status_t st = {};
-        st.flags = ACL_SWARM_BAD_INPUT;  // the control kernels leave the swarm alone
-        A.cst[b] = st;
-      }
-    }
-    if (bad) return;
+    const bool bad = fleet_input_check<kLat>(A, b, false, differs);
+    // (a good swarm's fidx_eff is the pre kernel's, which skips a bad one)
+    fleet_input_mark(A, b, bad);
+    if (bad) return;  // block-uniform
   } else {
     if (A.skip[b] != 0 || A.fidx_eff[b] < 0) {  // block-uniform: BAD_INPUT, or a finished trial
       if (A.vflags_hist && tid < n) A.vflags_hist[((size_t)A.k * A.B + b) * n + tid] = 0;
       return;
     }
-    if (tid < 3) cnt_s[tid] = 0;
-    if (tid == 0) adopt0_s = 0;
-    __syncthreads();
-    int x = 0;
-    if (tid < n) {
-      x = A.vf[vb + tid];
-      if (x) {
-        A.vflags[vb + tid] |= x;
-        A.vf[vb + tid] = 0;
-        if (x & ACL_FLEET_V_ADOPTED) {
-          A.adopt_step[vb + tid] = A.step;
-          A.ctl_on[vb + tid] = 1;  // first_assignment_: the controller starts
-          if (tid == 0) adopt0_s = 1;
-        }
-      }
-      if (A.vflags_hist) A.vflags_hist[((size_t)A.k * A.B + b) * n + tid] = x;
-    }
-    const int nc = __popcll(__ballot((x & ACL_FLEET_V_CONSENSUS) != 0));
-    const int na = __popcll(__ballot((x & ACL_FLEET_V_ADOPTED) != 0));
-    const int ni = __popcll(__ballot((x & ACL_FLEET_V_INVALID) != 0));
-    if (lane == 0) {
-      if (nc) atomicAdd(&cnt_s[0], nc);
-      if (na) atomicAdd(&cnt_s[1], na);
-      if (ni) atomicAdd(&cnt_s[2], ni);
-    }
-    __syncthreads();
-    const int adopted = cnt_s[1];
-    if (tid == 0) {
-      const acl_fleet_status_t fs = A.status[b];
-      acl_fleet_episode_status_t s = A.fst[b];
-      s.ticks_run += fs.ticks_run;
-      s.flags |= fs.flags & ACL_FLEET_OVERFLOW;
-      s.n_consensus += cnt_s[0];
-      s.n_adopted += adopted;
-      s.n_invalid += cnt_s[2];
-      A.fst[b] = s;
-      if (adopt0_s) {
+    int x;
+    const int adopted = fleet_step_flags(A, b, x);
+    if (x & ACL_FLEET_V_ADOPTED) {
+      A.ctl_on[(size_t)b * n + tid] = 1;  // first_assignment_: the controller starts
+      if (tid == 0) {
         // vehicle 0's assignment message (supervisor.py:147-150)
         acl_trial_status_t* t = A.ts + b;
         t->received = 1;
@@ -479,44 +326,10 @@ __global__ void __launch_bounds__(kFtrBlock) fleet_trial_handoff_kernel(const Ft
       }
     }
     if (adopted == 0) return;  // the tables the vehicles fly are unchanged
-    // are the n rows one table? every entry against row 0's, a wave per row
-    for (int v = wv; v < n; v += kFtrBlock / 64) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const int j = lane + 64 * s;
-        if (j < n && rows[(size_t)v * n + j] != rows[j]) differs = true;
-      }
-    }
+    differs = fleet_rows_differ(A, b);
   }
-  const bool mixed = __syncthreads_or(__any(differs)) != 0;
-  // the control hand-off, in trial_adopt_kernel's layouts (trial.hip). The
-  // rows are permutations: checked at the start of the call, the commit
-  // writes identities and the fleet kernel adopts valid tables only.
-  if (!mixed) {
-    for (int j = tid; j < n; j += kFtrBlock) {
-      const uint16_t v = rows[j];
-      A.ctlPt[vb + j] = v;
-      A.P[vb + v] = (uint16_t)j;
-    }
-  } else {
-    uint16_t* crows = A.ctlRows + vb * n;
-    for (int v = wv; v < n; v += kFtrBlock / 64) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const int j = lane + 64 * s;
-        if (j < n) {
-          const uint16_t x = rows[(size_t)v * n + j];
-          crows[(size_t)v * n + j] = x;
-          if ((int)x == v) A.P[vb + v] = (uint16_t)j;  // the vehicle's point in its own row
-        }
-      }
-    }
-  }
-  if (tid == 0) {
-    A.ctlMode[b] = mixed ? 1 : 0;
-    A.ts[b].per_vehicle = mixed ? 1 : 0;
-    A.cst[b] = acl_swarm_status_t{};
-  }
+  const bool mixed = fleet_handoff_write(A, b, differs);
+  if (tid == 0) A.ts[b].per_vehicle = mixed ? 1 : 0;
 }
 
 }  // namespace acl_amd
@@ -547,22 +360,15 @@ constexpr FtrDelay kNoDelay = {nullptr, 0, 0, nullptr};
 
 // (after ftr_check; before anything else reads max_lat)
 acl_status_t ftr_delay(const acl_fleet_delay_trial_args_t* d, const char* who, FtrDelay* out) {
-  static char msg[200];
-  if (d->max_lat < 1 || d->max_lat > acl_amd::kFleetMaxLat) {
-    snprintf(msg, sizeof(msg), "%s: max_lat out of range [1, 64]", who);
-    return acl__set_error(msg);
-  }
+  if (d->max_lat < 1 || d->max_lat > acl_amd::kFleetMaxLat)
+    return acl_amd::fleet_error(who, "max_lat out of range [1, 64]");
   *out = FtrDelay{d->lat, d->max_lat, acl_amd::fleet_log_len(d->max_lat), nullptr};
   return ACL_OK;
 }
 
 // the argument errors of both entry points that need no pointer
 acl_status_t ftr_check(const acl_fleet_trial_args_t* a, int n, const char* who) {
-  static char msg[200];
-  auto fail = [&](const char* what) {
-    snprintf(msg, sizeof(msg), "%s: %s", who, what);
-    return acl__set_error(msg);
-  };
+  auto fail = [&](const char* what) { return acl_amd::fleet_error(who, what); };
   if (!a) return fail("null argument");
   if (n < 1 || n > acl_amd::kFleetMaxN) return fail("n out of range [1, 128]");
   if (a->B < 0 || a->K < 1 || a->steps < 0 || a->step0 < 0)
@@ -584,11 +390,7 @@ acl_status_t ftr_check(const acl_fleet_trial_args_t* a, int n, const char* who) 
 
 acl_status_t ftr_pointers(const acl_fleet_trial_args_t* a, int n, const char* who,
                           const FtrDelay& dl) {
-  static char msg[200];
-  auto fail = [&](const char* what) {
-    snprintf(msg, sizeof(msg), "%s: %s", who, what);
-    return acl__set_error(msg);
-  };
+  auto fail = [&](const char* what) { return acl_amd::fleet_error(who, what); };
   if (!a->fseq || !a->fidx || !a->q || !a->vel || !a->P || !a->ts || !a->ctl_on || !a->ring_u ||
       !a->ring_ca || !a->posf || !a->dist || !a->t_conv || !a->t_avoid || !a->n_assign ||
       !a->Pt || !a->open || !a->invalid || !a->just_received || !a->biditer || !a->price ||
@@ -678,7 +480,7 @@ acl_status_t ftr_init(const char* who, const acl_fleet_trial_args_t* a, int n, c
   if (hipMemsetAsync(a->workspace, 0, ftr_layout(n, a->B, a->queue_cap, dl.R).total, s) !=
       hipSuccess)
     return acl__set_error("hipMemsetAsync failed");
-  hipLaunchKernelGGL(fleet_trial_init_kernel, dim3(a->B), dim3(kFtrBlock), 0, s, D, A, I);
+  hipLaunchKernelGGL(fleet_trial_init_kernel, dim3(a->B), dim3(kFleetLoopBlock), 0, s, D, A, I);
   if (hipGetLastError() != hipSuccess)
     return acl__set_error("fleet_trial_init_kernel launch failed");
   return ACL_OK;
@@ -696,11 +498,7 @@ acl_status_t ftr_run(const char* who, const acl_formations_t* F, const acl_fleet
   if (B == 0 || a->steps == 0) return ACL_OK;
   acl_status_t r = ftr_pointers(a, n, who, dl);
   if (r != ACL_OK) return r;
-  if (F->n_formations < 1) {
-    static char msg[200];
-    snprintf(msg, sizeof(msg), "%s: n_formations < 1", who);
-    return acl__set_error(msg);
-  }
+  if (F->n_formations < 1) return fleet_error(who, "n_formations < 1");
   const bool delay = dl.R != 0;
   const FtrLayout W = ftr_layout(n, B, a->queue_cap, dl.R);
   unsigned char* ws = (unsigned char*)a->workspace;
@@ -710,22 +508,9 @@ acl_status_t ftr_run(const char* who, const acl_formations_t* F, const acl_fleet
   FtrArgs A = ftr_args(a, n, D, dl);
   A.F = F->n_formations;
 
-  // the ticks: the fleet kernel on the trial's state; its vflags are the
-  // step's own (A.vf, cleared by the hand-off), the caller's stay sticky
-  acl_fleet_lossy_args_t fl = {};
-  if (dl.link) fl.link = *dl.link;
-  acl_fleet_delay_args_t& fd = fl.delay;
-  fd.lat = dl.lat; fd.max_lat = dl.max_lat;
-  acl_fleet_auction_args_t& fa = fd.base;
-  fa.B = B; fa.ticks = a->ticks_per_step; fa.max_iter = a->max_iter; fa.queue_cap = a->queue_cap;
-  fa.fidx = A.fidx_eff; fa.q = a->q; fa.cmd = A.cmd; fa.Pt = a->Pt; fa.open = a->open;
-  fa.invalid = a->invalid; fa.just_received = a->just_received; fa.biditer = a->biditer;
-  fa.price = a->price; fa.who = a->who; fa.Rt = a->Rt; fa.final_price = a->final_price;
-  fa.final_who = a->final_who; fa.done_tick = a->done_tick; fa.vflags = A.vf;
-  fa.n_thrown = a->n_thrown; fa.n_tally = a->n_tally; fa.queue_len = a->queue_len;
-  fa.status = a->status;
-  fa.workspace = ws + W.fleet;
-  fa.workspace_bytes = (size_t)B * fleet_layout(n, a->queue_cap, dl.R).total;
+  // the ticks: the fleet kernel on the trial's state, the pre kernel's commands
+  acl_fleet_lossy_args_t fl = fleet_tick_args(a, n, W, dl.lat, dl.max_lat, dl.link);
+  fl.delay.base.cmd = A.cmd;
 
   // the control stage on the current formations (a->fidx is in range for every
   // swarm the control kernels do not skip) and the hand-off region
@@ -741,10 +526,10 @@ acl_status_t ftr_run(const char* who, const acl_formations_t* F, const acl_fleet
 
   // the call's input check and its hand-off from the rows alone
   if (delay)
-    hipLaunchKernelGGL((fleet_trial_handoff_kernel<true, true>), dim3(B), dim3(kFtrBlock), 0, s,
-                       A);
+    hipLaunchKernelGGL((fleet_trial_handoff_kernel<true, true>), dim3(B), dim3(kFleetLoopBlock), 0,
+                       s, A);
   else
-    hipLaunchKernelGGL(fleet_trial_handoff_kernel<true>, dim3(B), dim3(kFtrBlock), 0, s, A);
+    hipLaunchKernelGGL(fleet_trial_handoff_kernel<true>, dim3(B), dim3(kFleetLoopBlock), 0, s, A);
   if (hipGetLastError() != hipSuccess)
     return acl__set_error("fleet_trial_handoff_kernel launch failed");
   const acl_episode_params_t& ep = a->tp.ep;
@@ -752,16 +537,14 @@ acl_status_t ftr_run(const char* who, const acl_formations_t* F, const acl_fleet
     D.step = A.step = a->step0 + k;
     D.k = A.k = k;
     if (delay)
-      hipLaunchKernelGGL(fleet_trial_pre_kernel<true>, dim3(B), dim3(kFtrBlock), 0, s, A);
+      hipLaunchKernelGGL(fleet_trial_pre_kernel<true>, dim3(B), dim3(kFleetLoopBlock), 0, s, A);
     else
-      hipLaunchKernelGGL(fleet_trial_pre_kernel<false>, dim3(B), dim3(kFtrBlock), 0, s, A);
+      hipLaunchKernelGGL(fleet_trial_pre_kernel<false>, dim3(B), dim3(kFleetLoopBlock), 0, s, A);
     if (hipGetLastError() != hipSuccess)
       return acl__set_error("fleet_trial_pre_kernel launch failed");
-    r = dl.link ? acl_fleet_lossy_auction_batch(F, &fl, stream)
-        : delay ? acl_fleet_delay_auction_batch(F, &fd, stream)
-                : acl_fleet_auction_batch(F, &fa, stream);
+    r = fleet_run_ticks(F, fl, dl.link != nullptr, nullptr, stream);
     if (r != ACL_OK) return r;
-    hipLaunchKernelGGL(fleet_trial_handoff_kernel<false>, dim3(B), dim3(kFtrBlock), 0, s, A);
+    hipLaunchKernelGGL(fleet_trial_handoff_kernel<false>, dim3(B), dim3(kFleetLoopBlock), 0, s, A);
     if (hipGetLastError() != hipSuccess)
       return acl__set_error("fleet_trial_handoff_kernel launch failed");
     r = run_control(F, &cs, s, CTL_MIXED);

@@ -217,6 +217,21 @@ struct SecProf {
 #define ACL_AUCTION_NO_PUBLISH 0
 #endif
 
+// Lean START (ACL_START_LEAN, default on): the runner-up of a START select
+// feeds its decision margin only, so the instantiations without the margin
+// (MG false: skip_margin) track no runner-up price in the price loop, run no
+// second atomic pass over the borrowed `none` row and read no alignment gap;
+// the instantiations with the margin are the same code as with the knob off.
+#ifndef ACL_START_LEAN
+#define ACL_START_LEAN 1
+#endif
+// first_who as one v_readlane per chunk and scalar selects (ACL_FIRST_WHO_RL,
+// default on) instead of a select chain over (lane, source) and one v_readlane
+// of the selected source: a vector select per lane less for NC = 2.
+#ifndef ACL_FIRST_WHO_RL
+#define ACL_FIRST_WHO_RL 1
+#endif
+
 // Column maxima (ACL_CBAA_COLMAX, default on): an entry's price never falls
 // (updateTaskAssignment keeps the best of a closed neighbourhood that holds
 // the vehicle itself; a select raises it), so a column's highest key is the
@@ -352,8 +367,19 @@ __device__ __forceinline__ int wave_select(int n, int TS, int v, int lane, const
 }
 
 // `who` of the first holder (lowest vehicle index) of a level
+// (no holder at all: the value is arbitrary and no caller uses it -- an
+// empty level hits nobody and ties with nobody)
 template <int NC>
 __device__ __forceinline__ int first_who(const unsigned long long (&h)[NC], const int (&wu)[NC]) {
+#if ACL_FIRST_WHO_RL
+  int who = __builtin_amdgcn_readlane(wu[NC - 1], (__ffsll((long long)h[NC - 1]) - 1) & 63);
+#pragma unroll
+  for (int c = NC - 2; c >= 0; --c) {
+    const int x = __builtin_amdgcn_readlane(wu[c], (__ffsll((long long)h[c]) - 1) & 63);
+    who = h[c] ? x : who;
+  }
+  return who;
+#endif
   int hl = 0, src = wu[0];
 #pragma unroll
   for (int c = NC - 1; c >= 0; --c)
@@ -810,6 +836,8 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
   static_assert((kCW & (kCW - 1)) == 0, "ACL_CBAA_WAVES: a power of two");
   // the CBAA rounds' decision-margin work (MG false: skip_margin)
   constexpr bool kMarg = MG && !ACL_AUCTION_NO_MARGIN;
+  // the START selects' runner-up prices and the alignment gap (margin inputs)
+  constexpr bool kSec = MG || !ACL_START_LEAN;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int n = P.n;
   const ALayout L = make_alayout(n);
@@ -909,7 +937,8 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
     const double* gout = reinterpret_cast<const double*>(wsa);
     for (int k = tid; k < 6 * n; k += kAB) out[k] = gout[k];
     for (int i = tid; i < n; i += kAB) itm[i] = wsa[(size_t)n * 48 + i];
-    if (tid == 0) agap = *reinterpret_cast<const unsigned long long*>(wsa + (size_t)n * 48 + a16(n));
+    if (kSec && tid == 0)
+      agap = *reinterpret_cast<const unsigned long long*>(wsa + (size_t)n * 48 + a16(n));
   }
   __syncthreads();
   if (tid == 0) {
@@ -1021,7 +1050,7 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
     block_min_gap(margw, galign);
   } else if (ACL_ALIGN_PREFETCH) {
     // (out and itm were filled in phase 0)
-    if (tid == 0) atomicMin(margw, agap);
+    if (kSec && tid == 0) atomicMin(margw, agap);
   } else {
     const unsigned char* wsa = P.ws + P.W.align + (size_t)b * P.W.align_stride;
     const int nitems = *reinterpret_cast<const int*>(wsa + (size_t)n * 48 + a16(n) + 8);
@@ -1104,7 +1133,7 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
         if (kGen) nonfin |= (c != c);
         // strict > from max = 0 (NaN never wins, never becomes the runner-up)
         const bool gt = c > pbest;
-        psec = gt ? pbest : (c > psec ? c : psec);
+        if (kSec) psec = gt ? pbest : (c > psec ? c : psec);
         pbj = gt ? j : pbj;
         pbest = gt ? c : pbest;
       }
@@ -1117,7 +1146,8 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
       atomicMax(&W1[pv], ((unsigned long long)__float_as_uint(pbest) << 8) |
                              (unsigned long long)(255 - pbj));
     if (__any(nonfin) && lane == 0) misc[M_NONFIN] = 1;
-    for (int jj = tid; jj < n; jj += kAB) W2[jj] = 0u;  // (the `none` row: zeros again below)
+    // (the `none` row: price 0; with the runner-up pass, zeros again below)
+    for (int jj = tid; jj < n; jj += kAB) W2[jj] = 0u;
   }
   // per-lane neighbourhood masks of this lane's vehicles (lane + 64 c)
   unsigned long long vm[NC][NC];
@@ -1145,7 +1175,7 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
     for (int k = tid; k < n * (TS / 4); k += kAB) T32[k] = fill;
     if (ACL_CBAA_COLMAX)
       for (int jj = tid; jj < n; jj += kAB) cmax[jj] = 1u;  // the `none` key
-    if (pact && pbj >= 0) {
+    if (kSec && pact && pbj >= 0) {
       const int js = 255 - (int)(W1[pv] & 255ull);
       const float cand = pbj == js ? psec : pbest;
       if (cand > 0.0f) atomicMax(&W2[pv], __float_as_uint(cand));
@@ -1155,8 +1185,11 @@ __global__ void __launch_bounds__(kAB, kAB == 128 ? ACL_AUCTION_OCC_SMALL : 6)
   if (tid < n) {
     const int v = tid;
     const unsigned long long w = W1[v];
-    const unsigned sec = W2[v];
-    W2[v] = 0u;  // the `none` row's price 0 again
+    unsigned sec = 0u;
+    if (kSec) {
+      sec = W2[v];
+      W2[v] = 0u;  // the `none` row's price 0 again
+    }
     if (w) {
       const int js = 255 - (int)(w & 255ull);
       T[v * TS + js] = (unsigned char)v;

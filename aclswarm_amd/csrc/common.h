@@ -456,6 +456,28 @@ __device__ __forceinline__ double acl_atan_b_vote(double x, const double* tab) {
 #ifndef ACL_PRICE_NEWTON
 #define ACL_PRICE_NEWTON 1  // Newton steps on the hardware reciprocal square root
 #endif
+// The range test on x's high dword (ACL_PRICE_HIWORD, default on): one
+// unsigned compare, xh - kPriceHiLo < kPriceHiHi - kPriceHiLo, that is
+// kPriceHiLo <= xh < kPriceHiHi, instead of two f64 compares and an and.
+// Doubles of one sign order as their bit patterns, and xh is the pattern's
+// upper half, so xh >= W means x >= the double (W << 32) and xh < W means
+// x < (W << 32), for a non-negative x.
+//   1e-6 = 0x3EB0C6F7'A0B5ED8D: kPriceHiLo = 0x3EB0C6F7 + 1, so every
+//     admitted x >= 0x3EB0C6F8'00000000 > 1e-6 (the first double left out at
+//     this end is 1e-6's successor; 2^32 - 0xA0B5ED8D patterns, a relative
+//     width of 1.5e-7, move to the IEEE expression);
+//   1e60 = 0x4C63E9E4'E4C2F344: kPriceHiHi = 0x4C63E9E4, so every admitted
+//     x < 0x4C63E9E4'00000000 < 1e60 (0xE4C2F344 patterns move).
+// Both constants lie inside (1e-6, 1e60): the admitted set is a subset of the
+// old one, and an x that newly fails takes the IEEE expression, which is the
+// reference -- the results are the same bits. What must fail does: a set sign
+// bit makes xh >= 0x80000000 and inf / NaN xh >= 0x7FF00000, both above
+// kPriceHiHi; zero and the subnormals have xh < 0x00100000, below kPriceHiLo,
+// and the difference wraps to a large unsigned value.
+#ifndef ACL_PRICE_HIWORD
+#define ACL_PRICE_HIWORD 1
+#endif
+constexpr unsigned kPriceHiLo = 0x3EB0C6F8u, kPriceHiHi = 0x4C63E9E4u;
 __device__ __forceinline__ float acl_price(double x) {
 #if ACL_PRICE_RSQ
   double r = __builtin_amdgcn_rsq(x);
@@ -475,7 +497,14 @@ __device__ __forceinline__ float acl_price(double x) {
   const double lo = 1e-200;
 #endif
   const unsigned r29 = (unsigned)((unsigned long long)__double_as_longlong(y) & ((1ull << 29) - 1ull));
+#if ACL_PRICE_RSQ && ACL_PRICE_HIWORD
+  const unsigned xh = (unsigned)((unsigned long long)__double_as_longlong(x) >> 32);
+  // (unsigned: one compare)
+  const bool fast = xh - kPriceHiLo < kPriceHiHi - kPriceHiLo && (r29 - (1u << 28) + 1024u) > 2048u;
+  (void)lo;
+#else
   const bool fast = x > lo && x < 1e60 && (r29 - (1u << 28) + 1024u) > 2048u;
+#endif
   float c = (float)y;
   if (!fast) c = (float)(1.0 / (sqrt(x) + 1e-8));
   return c;

@@ -12,7 +12,8 @@
 // instruction budget -- the fused kernel is bound by the vector ALU
 // (DESIGN.md §4):
 //   * per-point data packed in one LDS row {q, p, |p.xy|^2, p.z^2}, rows
-//     padded to a multiple of 8 with zeros, so no lane needs a bounds test;
+//     padded to a multiple of 8 (zeros, but for q: below), so no lane needs a
+//     bounds test;
 //   * a lane's record index from one LDS word per direction (etab) and a
 //     masked popcount; the diagonal tiles' lane masks are scalar constants;
 //   * the records of tile t + 1 load into the other set of a two-set
@@ -39,7 +40,24 @@
 //     exact test, which every thread of the workgroup then runs on a share
 //     of the rows (gain_epilogue's test); a vehicle not flagged has no other
 //     vehicle within the threshold, so the outcome is the same, without an
-//     n^2 loop per swarm.
+//     n^2 loop per swarm;
+//   * the padded rows i in [n, R) far away instead of masked out of that
+//     test: q = (2^500 (i - n + 1), 0, 0), everything else of the row zero.
+//     Two padded rows are at least 2^500 apart and so are a padded and a real
+//     row of ordinary coordinates, so the test fails there by itself and a
+//     tile needs no mask of its real rows and columns (two compares, two
+//     64-bit shifts, a 64-bit multiply and selects on the scalar unit, per
+//     tile); only the diagonal's strict upper triangle and the dead half of an
+//     odd packed tile (real pairs, the wrong way round) are still masked.
+//     Every product stays finite (s2 <= 49 * 2^1000). No padded value reaches a
+//     sum: a padded row has no adjacency bit and a padded column is masked
+//     out of every adjacency word, so a padded lane is never in mx | my, its
+//     Fxy = Fz = 0, and 0 * 2^500 = 0 as 0 * 0 was. A real coordinate that is
+//     not ordinary (NaN, or of the order of 2^500) can raise a spurious flag on
+//     a padded and on a real row; a flag only sends rows to the exact pass,
+//     which walks real rows and real vehicles only and decides by its own
+//     test, so it costs that pass and never changes its result (nearb has a
+//     bit for every row below R <= 128).
 // Gates, gate margin and collision flags are decided by the same expressions
 // as in pair_gain_swarm (bit-identical); u / u_safe are tolerance parity.
 #pragma once
@@ -69,6 +87,17 @@
 #endif
 #ifndef ACL_FUSED_ATAN_VOTE
 #define ACL_FUSED_ATAN_VOTE 1
+#endif
+// 1: the padded rows sit far away (header comment) and the candidate test
+// needs no per-tile mask of the real rows and columns; 0: zeros past n and
+// the masks (A/B builds)
+#ifndef ACL_FUSED_FARPAD
+#define ACL_FUSED_FARPAD 1
+#endif
+// 1: the regular tile loop's "a next tile follows" flag held in a scalar
+// register (A/B builds: 0, a plain bool)
+#ifndef ACL_FUSED_MORE_SGPR
+#define ACL_FUSED_MORE_SGPR 1
 #endif
 #if ACL_FUSED_SQRT_VOTE
 #define ACL_FUSED_PAIR_E pair_e_vote
@@ -304,9 +333,9 @@ __device__ __forceinline__ void pair_gain_fused(KCtlParams* Pp, int b, int f,
     if (__any(qbad) && lane == 0) atomicOr(flags, 1u);
   }
   __syncthreads();
-  if (tid < R) {  // row i's q: vehicle Pt[i]'s (zeros past n)
+  if (tid < R) {  // row i's q: vehicle Pt[i]'s (past n: far away, see the header)
     const int i = tid;
-    double q0 = 0.0, q1 = 0.0, q2 = 0.0;
+    double q0 = ACL_FUSED_FARPAD ? 0x1p500 * (double)(i - n + 1) : 0.0, q1 = 0.0, q2 = 0.0;
     if (i < n) {
       const int v = Pt[i];
       q0 = qs[3 * v];
@@ -425,6 +454,16 @@ __device__ __forceinline__ void pair_gain_fused(KCtlParams* Pp, int b, int f,
         Jn = In;
       }
       const bool more = t + 1 < t1r;  // wave-uniform
+      // ACL_FUSED_MORE_SGPR: `more` is tested once, here (a scalar compare and
+      // branch). The record prefetches below run on the last tile as well: its
+      // "next" etab words are 0, so their masks are empty and every lane's
+      // loads take the offset past num_records (zeros, no memory access). With
+      // the prefetches behind `if (more)` the compiler carried the flag's
+      // negation to the later tests through a VGPR (v_cndmask, v_cmp) and
+      // branched on vcc twice more per tile. (Not with the gate margin: there
+      // the unconditional loads cost the small instantiations three more
+      // spilled VGPRs.)
+      constexpr bool kPre = ACL_FUSED_MORE_SGPR != 0 && !GM;
       // the next tile's etab words, read early (their latency hides here)
       unsigned xijn = 0u, xjin = 0u;
       if (more) {
@@ -439,11 +478,15 @@ __device__ __forceinline__ void pair_gain_fused(KCtlParams* Pp, int b, int f,
       const double s2 = pair_s2(q0, q1);
       {
         // collision candidates: every pair i < j of the swarm (edge or not)
+#if ACL_FUSED_FARPAD  // (a padded row is far from every other row)
+        const unsigned long long vm = I == J ? kTileUpStrict : ~0ull;
+#else
         const int nr = n - 8 * I, nc = n - 8 * J;
         const unsigned long long rows = nr >= 8 ? ~0ull : ((1ull << (8 * nr)) - 1ull);
         const unsigned long long cols =
             (nc >= 8 ? 0xFFull : ((1ull << nc) - 1ull)) * 0x0101010101010101ull;
         const unsigned long long vm = rows & cols & (I == J ? kTileUpStrict : ~0ull);
+#endif
         const unsigned long long nm = __ballot(!(s2 > fcst(cst, FC_THR2))) & vm;
         if (nm) {  // rare: flag both rows for the epilogue's exact test
           if (lanebit_u64(nm)) {
@@ -486,7 +529,7 @@ __device__ __forceinline__ void pair_gain_fused(KCtlParams* Pp, int b, int f,
         }
       }
       unsigned long long mxn = 0ull, myn = 0ull;
-      if (more) {  // the next tile's (i, j) records into X
+      if (kPre || more) {  // the next tile's (i, j) records into X
         mxn = rec_mask(xijn, c, In == Jn, kTileUpIncl);
         rec_load(xijn, c, mxn, X);
       }
@@ -503,7 +546,7 @@ __device__ __forceinline__ void pair_gain_fused(KCtlParams* Pp, int b, int f,
           ct2 = ((0.0 * q0 + 0.0 * q1) + Y.a[4] * q2) + f2;
         }
       }
-      if (more) {  // the next tile's (j, i) records into Y
+      if (kPre || more) {  // the next tile's (j, i) records into Y
         myn = rec_mask(xjin, r, In == Jn, kTileUpStrict);
         rec_load(xjin, r, myn, Y);
       }
@@ -560,8 +603,14 @@ __device__ __forceinline__ void pair_gain_fused(KCtlParams* Pp, int b, int f,
       {
         // collision candidates: the real columns of both halves (every row of
         // a live half is real: Ih <= nb - 2; i < j throughout)
+#if ACL_FUSED_FARPAD
+        // (a padded column is far from every row; hm stays: the dead half of
+        // an odd tile holds real pairs of the diagonal block, i >= j among them)
+        const unsigned long long vm = hm;
+#else
         const int nc = n - 8 * (nb - 1);  // 1 .. 4
         const unsigned long long vm = (((1ull << nc) - 1ull) * 0x1111111111111111ull) & hm;
+#endif
         const unsigned long long nm = __ballot(!(s2 > fcst(cst, FC_THR2))) & vm;
         if (nm) {
           if (lanebit_u64(nm)) {

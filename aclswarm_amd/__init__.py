@@ -8,12 +8,13 @@ from . import _lib  # noqa: F401
 from ._lib import (FLAG_AGREE, FLAG_BAD_INPUT, FLAG_CA_ACTIVE, FLAG_CHANGED,  # noqa: F401
                    FLAG_NONFINITE, FLAG_VALID, STATUS_DTYPE, lib)
 
-__all__ = ["lib", "STATUS_DTYPE", "FleetEpisode", "FleetEstEpisode", "FleetTrial"]
+__all__ = ["lib", "STATUS_DTYPE", "FleetEpisode", "FleetEstEpisode", "FleetTrial",
+           "FleetEstTrial"]
 
 
 def __getattr__(name):
     # engine imports torch: loaded on first use, not with the package
-    if name in ("FleetEpisode", "FleetEstEpisode", "FleetTrial"):
+    if name in ("FleetEpisode", "FleetEstEpisode", "FleetTrial", "FleetEstTrial"):
         from . import engine
         return getattr(engine, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

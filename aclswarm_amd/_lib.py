@@ -47,6 +47,8 @@ EXPORTS = (
     "acl_fleet_lossy_trial_batch",
     "acl_fleet_localize_batch", "acl_fleet_est_auction_batch", "acl_fleet_est_control_batch",
     "acl_fleet_est_episode_workspace_bytes", "acl_fleet_est_episode_batch",
+    "acl_fleet_est_trial_workspace_bytes", "acl_fleet_est_trial_init",
+    "acl_fleet_est_trial_batch",
     "acl_default_episode_params", "acl_episode_workspace_bytes", "acl_episode_batch",
     "acl_default_trial_params", "acl_trial_workspace_bytes", "acl_trial_init", "acl_trial_batch",
     "acl_fleet_trial_workspace_bytes", "acl_fleet_trial_init", "acl_fleet_trial_batch",
@@ -345,6 +347,15 @@ class FleetLossyTrialArgs(ct.Structure):
     _fields_ = [("delay", FleetDelayTrialArgs), ("link", FleetLoss)]
 
 
+class FleetEstTrialArgs(ct.Structure):
+    """acl_fleet_est_trial_args_t (added within ABI 11): the trials on each
+    vehicle's own estimates."""
+    _fields_ = [("lossy", FleetLossyTrialArgs), ("track_every", ct.c_int32),
+                ("diag", ct.c_int32)] + [
+        (n, ct.c_void_p) for n in ("loc_stamp", "loc_est", "loc_round", "loc_n_lost", "loc_Pt",
+                                   "xst", "err2_hist")]
+
+
 class GemmJobRec(ct.Structure):
     """acl_internal_gemm_job_t (csrc/admm.hip, a test hook's record): GemmJob
     (csrc/gemm_f64.h) field for field; pointers are device addresses."""
@@ -487,6 +498,13 @@ def lib():
     L.acl_fleet_est_episode_batch.argtypes = [ct.POINTER(Formations),
                                               ct.POINTER(FleetEstEpisodeArgs), VP]
     L.acl_fleet_est_episode_batch.restype = ct.c_int
+    L.acl_fleet_est_trial_workspace_bytes.argtypes = [I32, I32, I32, I32]
+    L.acl_fleet_est_trial_workspace_bytes.restype = SZ
+    L.acl_fleet_est_trial_init.argtypes = [ct.POINTER(FleetEstTrialArgs), I32, VP]
+    L.acl_fleet_est_trial_init.restype = ct.c_int
+    L.acl_fleet_est_trial_batch.argtypes = [ct.POINTER(Formations),
+                                            ct.POINTER(FleetEstTrialArgs), VP]
+    L.acl_fleet_est_trial_batch.restype = ct.c_int
     L.acl_write_assignment_log.argtypes = [ct.c_char_p, I32, VP, VP, VP, VP, VP, VP]
     L.acl_write_assignment_log.restype = ct.c_int
     L.acl_read_assignment_log.argtypes = [ct.c_char_p, ct.POINTER(I32), VP, VP, VP, VP, VP, VP]

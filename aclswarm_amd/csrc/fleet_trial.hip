@@ -49,6 +49,23 @@
 // kernel's commit acts on the delay layout, where what is in flight lives in
 // the publication logs and nothing is copied aside.
 //
+// acl_fleet_est_trial_init / acl_fleet_est_trial_batch are the trials on each
+// vehicle's own estimates (ftr_init, ftr_run with an FtrOwn block): after the
+// pre kernel a gossip round of acl_fleet_localize_batch on the steps
+// s % track_every == 0, subscribed under the vehicles' LOCALIZATION rows loc_Pt
+// (the assignment a vehicle last published, which a commit does not touch);
+// the step's ticks those of acl_fleet_est_auction_batch; the control step
+// acl_fleet_est_control_batch on the vehicles' tables; all three through their
+// public entries. Two kernels are new, defined at the end of the file so that
+// the code of the kernels above is what it was:
+//   fleet_trial_est_init_kernel  identity loc_Pt, fresh trackers, xst 0
+//   fleet_trial_est_post_kernel  between the ticks and the hand-off (which
+//                                consumes the step's flags vf): an adopter's
+//                                row -> loc_Pt; the round's localize status ->
+//                                xst; <true> (diag != 0): how wrong the tables
+//                                are against the true q, err2_nbr over the
+//                                running controllers only
+//
 // Compiled with -ffp-contract=off (trial_dev.h).
 #include "common.h"
 #include "fleet_loop_dev.h"
@@ -62,16 +79,24 @@ namespace acl_amd {
 
 // Workspace: the loops' common regions (fleet_loop_dev.h), then the trial's own.
 struct FtrLayout : FleetLoopLayout {
-  size_t zstep, total;
+  size_t zstep, lst, ecs, total;
 };
 
 // R 0: acl_fleet_auction_batch's fleet part, else the delay layout's with
-// publication logs of R entries
-inline FtrLayout ftr_layout(int n, int B, int cap, int R = 0) {
+// publication logs of R entries. own: the status arrays of the localize and
+// control entries follow (the own-estimate entry); nothing before them moves.
+inline FtrLayout ftr_layout(int n, int B, int cap, int R = 0, bool own = false) {
   FtrLayout L;
   static_cast<FleetLoopLayout&>(L) = fleet_loop_layout(n, B, cap, R);
   L.zstep = L.end;  // [B] u8: the swarm commits a formation this step
-  L.total = ws_al(L.zstep + (size_t)B);
+  size_t o = ws_al(L.zstep + (size_t)B);
+  L.lst = L.ecs = o;
+  if (own) {
+    o = ws_al(o + (size_t)B * sizeof(acl_fleet_localize_status_t));
+    L.ecs = o;
+    o = ws_al(o + (size_t)B * sizeof(acl_fleet_control_status_t));
+  }
+  L.total = o;
   return L;
 }
 
@@ -104,6 +129,37 @@ struct FtrInit {
   int32_t* n_tally;
   int32_t* queue_len;
   acl_fleet_status_t* status;
+};
+
+// The own-estimate entry's arguments beside acl_fleet_lossy_trial_args_t.
+struct FtrOwn {
+  int track_every, diag;
+  int32_t* loc_stamp;
+  double* loc_est;
+  int32_t* loc_round;
+  int32_t* loc_n_lost;
+  uint16_t* loc_Pt;
+  acl_fleet_est_episode_status_t* xst;
+  double* err2_hist;
+};
+
+// what fleet_trial_est_post_kernel reads and writes
+struct FtrPost {
+  int n, B, k;
+  int round;  // != 0: the step ran a gossip round, lst is its status
+  const uint8_t* skip;
+  const int32_t* fidx_eff;
+  const int32_t* vf;  // the flags of this step's ticks, before the hand-off takes them
+  const uint8_t* ctl_on;
+  const uint64_t* adj;
+  const double* q;
+  const double* est;
+  const int32_t* stamp;
+  const uint16_t* Pt;
+  uint16_t* loc_Pt;
+  const acl_fleet_localize_status_t* lst;
+  acl_fleet_est_episode_status_t* xst;
+  double* err2_hist;
 };
 
 // ---- the start of a trial (acl_fleet_trial_init) ------------------------------
@@ -358,6 +414,10 @@ struct FtrDelay {
 };
 constexpr FtrDelay kNoDelay = {nullptr, 0, 0, nullptr};
 
+// the own-estimate entry's two kernels (at the end of the file)
+acl_status_t ftr_est_init_launch(const acl_amd::FtrOwn& O, int n, int B, hipStream_t s);
+acl_status_t ftr_est_post_launch(const acl_amd::FtrPost& X, bool diag, hipStream_t s);
+
 // (after ftr_check; before anything else reads max_lat)
 acl_status_t ftr_delay(const acl_fleet_delay_trial_args_t* d, const char* who, FtrDelay* out) {
   if (d->max_lat < 1 || d->max_lat > acl_amd::kFleetMaxLat)
@@ -389,7 +449,7 @@ acl_status_t ftr_check(const acl_fleet_trial_args_t* a, int n, const char* who) 
 }
 
 acl_status_t ftr_pointers(const acl_fleet_trial_args_t* a, int n, const char* who,
-                          const FtrDelay& dl) {
+                          const FtrDelay& dl, const acl_amd::FtrOwn* own = nullptr) {
   auto fail = [&](const char* what) { return acl_amd::fleet_error(who, what); };
   if (!a->fseq || !a->fidx || !a->q || !a->vel || !a->P || !a->ts || !a->ctl_on || !a->ring_u ||
       !a->ring_ca || !a->posf || !a->dist || !a->t_conv || !a->t_avoid || !a->n_assign ||
@@ -402,9 +462,13 @@ acl_status_t ftr_pointers(const acl_fleet_trial_args_t* a, int n, const char* wh
   if (dl.link && !dl.link->loss) return fail("loss is NULL");
   if (dl.link && !dl.link->seed) return fail("seed is NULL");
   if (dl.link && !dl.link->n_lost) return fail("n_lost is NULL");
-  if (a->workspace_bytes < acl_amd::ftr_layout(n, a->B, a->queue_cap, dl.R).total)
-    return fail(dl.R ? "workspace_bytes is too small (acl_fleet_delay_trial_workspace_bytes)"
-                     : "workspace_bytes is too small (acl_fleet_trial_workspace_bytes)");
+  if (own && (!own->loc_stamp || !own->loc_est || !own->loc_round || !own->loc_n_lost ||
+              !own->loc_Pt || !own->xst))
+    return fail("loc_stamp, loc_est, loc_round, loc_n_lost, loc_Pt or xst is NULL");
+  if (a->workspace_bytes < acl_amd::ftr_layout(n, a->B, a->queue_cap, dl.R, own != nullptr).total)
+    return fail(own    ? "workspace_bytes is too small (acl_fleet_est_trial_workspace_bytes)"
+                : dl.R ? "workspace_bytes is too small (acl_fleet_delay_trial_workspace_bytes)"
+                       : "workspace_bytes is too small (acl_fleet_trial_workspace_bytes)");
   return ACL_OK;
 }
 
@@ -461,12 +525,14 @@ acl_amd::FtrArgs ftr_args(const acl_fleet_trial_args_t* a, int n, const acl_amd:
 }
 
 // acl_fleet_trial_init and acl_fleet_delay_trial_init (after ftr_check): the
-// same kernel; the zero-filled workspace is the entry's own layout.
+// same kernel; the zero-filled workspace is the entry's own layout. own
+// (acl_fleet_est_trial_init): the workspace with its tail, and the
+// own-estimate entry's arrays.
 acl_status_t ftr_init(const char* who, const acl_fleet_trial_args_t* a, int n, const FtrDelay& dl,
-                      void* stream) {
+                      void* stream, const acl_amd::FtrOwn* own = nullptr) {
   using namespace acl_amd;
   if (a->B == 0) return ACL_OK;
-  const acl_status_t r = ftr_pointers(a, n, who, dl);
+  const acl_status_t r = ftr_pointers(a, n, who, dl, own);
   if (r != ACL_OK) return r;
   const TrialDev D = ftr_trial_dev(a, n, dl);
   const FtrArgs A = ftr_args(a, n, D, dl);
@@ -477,30 +543,34 @@ acl_status_t ftr_init(const char* who, const acl_fleet_trial_args_t* a, int n, c
   hipStream_t s = (hipStream_t)stream;
   // freshly constructed auctioneers: empty queues and buckets, nothing in
   // flight, tick 0 (and the CA counter, the hand-off region, the step's flags)
-  if (hipMemsetAsync(a->workspace, 0, ftr_layout(n, a->B, a->queue_cap, dl.R).total, s) !=
-      hipSuccess)
+  const size_t ws_bytes = ftr_layout(n, a->B, a->queue_cap, dl.R, own != nullptr).total;
+  if (hipMemsetAsync(a->workspace, 0, ws_bytes, s) != hipSuccess)
     return acl__set_error("hipMemsetAsync failed");
   hipLaunchKernelGGL(fleet_trial_init_kernel, dim3(a->B), dim3(kFleetLoopBlock), 0, s, D, A, I);
   if (hipGetLastError() != hipSuccess)
     return acl__set_error("fleet_trial_init_kernel launch failed");
-  return ACL_OK;
+  return own ? ftr_est_init_launch(*own, n, a->B, s) : ACL_OK;
 }
 
 // The host loop of acl_fleet_trial_batch, acl_fleet_delay_trial_batch and
 // acl_fleet_lossy_trial_batch (after ftr_check). With dl.R the ticks are
 // acl_fleet_delay_auction_batch's under (dl.lat, dl.max_lat) on the delay
 // workspace layout; with dl.link acl_fleet_lossy_auction_batch's under it.
+// own (with dl.link): the trial on own estimates -- after the pre kernel a
+// gossip round every track_every steps under loc_Pt, the ticks
+// acl_fleet_est_auction_batch's, the post kernel, the control step
+// acl_fleet_est_control_batch's.
 acl_status_t ftr_run(const char* who, const acl_formations_t* F, const acl_fleet_trial_args_t* a,
-                     const FtrDelay& dl, void* stream) {
+                     const FtrDelay& dl, void* stream, const acl_amd::FtrOwn* own = nullptr) {
   using namespace acl_amd;
   const int n = F->n;
   const int B = a->B;
   if (B == 0 || a->steps == 0) return ACL_OK;
-  acl_status_t r = ftr_pointers(a, n, who, dl);
+  acl_status_t r = ftr_pointers(a, n, who, dl, own);
   if (r != ACL_OK) return r;
   if (F->n_formations < 1) return fleet_error(who, "n_formations < 1");
   const bool delay = dl.R != 0;
-  const FtrLayout W = ftr_layout(n, B, a->queue_cap, dl.R);
+  const FtrLayout W = ftr_layout(n, B, a->queue_cap, dl.R, own != nullptr);
   unsigned char* ws = (unsigned char*)a->workspace;
   hipStream_t s = (hipStream_t)stream;
   TrialDev D = ftr_trial_dev(a, n, dl);
@@ -524,6 +594,29 @@ acl_status_t ftr_run(const char* who, const acl_formations_t* F, const acl_fleet
   if (hipMemsetAsync(D.ca_count, 0, kCaCounterBytes, s) != hipSuccess)
     return acl__set_error("hipMemsetAsync failed");
 
+  // the trial on own estimates: the three public entries' arguments. The
+  // gossip subscribes under loc_Pt and sees the formation of this step (-1 for
+  // a finished trial, as the ticks and the control step do).
+  acl_fleet_localize_args_t lo = {};
+  acl_fleet_est_control_args_t ec = {};
+  FtrPost X = {};
+  if (own) {
+    acl_fleet_localize_status_t* lst =
+        reinterpret_cast<acl_fleet_localize_status_t*>(ws + W.lst);
+    lo.B = B; lo.rounds = 1; lo.q_rounds = 1; lo.fidx = A.fidx_eff; lo.Pt = own->loc_Pt;
+    lo.q = a->q; lo.stamp = own->loc_stamp; lo.est = own->loc_est; lo.round = own->loc_round;
+    lo.loss = dl.link->loss; lo.seed = dl.link->seed; lo.n_lost = own->loc_n_lost;
+    lo.status = lst;
+    ec.B = B; ec.fidx = A.fidx_eff; ec.est = own->loc_est; ec.vel = a->vel; ec.Pt = a->Pt;
+    ec.u = cs.u; ec.u_safe = cs.u_safe; ec.ca_flag = cs.ca_flag;
+    ec.status = reinterpret_cast<acl_fleet_control_status_t*>(ws + W.ecs);
+    ec.cntrl = a->cntrl; ec.safety = a->safety;
+    X.n = n; X.B = B; X.skip = A.skip; X.fidx_eff = A.fidx_eff; X.vf = A.vf;
+    X.ctl_on = a->ctl_on; X.adj = F->adj; X.q = a->q; X.est = own->loc_est;
+    X.stamp = own->loc_stamp; X.Pt = a->Pt; X.loc_Pt = own->loc_Pt; X.lst = lst;
+    X.xst = own->xst; X.err2_hist = own->err2_hist;
+  }
+
   // the call's input check and its hand-off from the rows alone
   if (delay)
     hipLaunchKernelGGL((fleet_trial_handoff_kernel<true, true>), dim3(B), dim3(kFleetLoopBlock), 0,
@@ -542,12 +635,25 @@ acl_status_t ftr_run(const char* who, const acl_formations_t* F, const acl_fleet
       hipLaunchKernelGGL(fleet_trial_pre_kernel<false>, dim3(B), dim3(kFleetLoopBlock), 0, s, A);
     if (hipGetLastError() != hipSuccess)
       return acl__set_error("fleet_trial_pre_kernel launch failed");
-    r = fleet_run_ticks(F, fl, dl.link != nullptr, nullptr, stream);
+    if (own && D.step % own->track_every == 0) {
+      // after this step's commit; the round senses q as it stands at the start of the step
+      r = acl_fleet_localize_batch(F, &lo, stream);
+      if (r != ACL_OK) return r;
+      X.round = 1;
+    } else {
+      X.round = 0;
+    }
+    r = fleet_run_ticks(F, fl, dl.link != nullptr, own ? own->loc_est : nullptr, stream);
     if (r != ACL_OK) return r;
+    if (own) {
+      X.k = k;
+      r = ftr_est_post_launch(X, own->diag != 0, s);
+      if (r != ACL_OK) return r;
+    }
     hipLaunchKernelGGL(fleet_trial_handoff_kernel<false>, dim3(B), dim3(kFleetLoopBlock), 0, s, A);
     if (hipGetLastError() != hipSuccess)
       return acl__set_error("fleet_trial_handoff_kernel launch failed");
-    r = run_control(F, &cs, s, CTL_MIXED);
+    r = own ? acl_fleet_est_control_batch(F, &ec, stream) : run_control(F, &cs, s, CTL_MIXED);
     if (r != ACL_OK) return r;
     hipLaunchKernelGGL(trial_traj_kernel<true>, dim3(B), dim3(kTrBlock), 0, s, D);
     if (hipGetLastError() != hipSuccess) return acl__set_error("trial_traj_kernel launch failed");
@@ -611,4 +717,238 @@ extern "C" acl_status_t acl_fleet_lossy_trial_batch(const acl_formations_t* F,
   r = ftr_delay(d, who, &dl);
   dl.link = &l->link;
   return r != ACL_OK ? r : ftr_run(who, F, &d->base, dl, stream);
+}
+
+// ---- the trials on each vehicle's own estimates ---------------------------------
+// (Below everything else, so that the kernels above are emitted as before.)
+namespace acl_amd {
+
+// acl_fleet_est_trial_init's additions: the localization rows are the
+// identity (LocalizationROS starts from the identity assignment), the trackers
+// are fresh, the record is empty. (A template, like the post kernel: hipcc
+// emits template instantiations after the file's other kernels.)
+template <class Own>
+__global__ void __launch_bounds__(kFleetLoopBlock) fleet_trial_est_init_kernel(const Own O,
+                                                                                 const int n) {
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
+  const size_t bn = (size_t)b * n;
+  for (size_t k = tid; k < (size_t)n * n; k += kFleetLoopBlock) {
+    const size_t i = bn * n + k;
+    O.loc_Pt[i] = (uint16_t)(k % n);
+    O.loc_stamp[i] = 0;
+    O.loc_est[3 * i] = 0.0;
+    O.loc_est[3 * i + 1] = 0.0;
+    O.loc_est[3 * i + 2] = 0.0;
+  }
+  for (int v = tid; v < n; v += kFleetLoopBlock) O.loc_n_lost[bn + v] = 0;
+  if (tid == 0) {
+    O.loc_round[b] = 0;
+    O.xst[b] = acl_fleet_est_episode_status_t{};
+  }
+}
+
+__device__ __forceinline__ double ftr_wave_max_gt(double m) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    // (the two 32-bit halves travel separately)
+    const int lo = __shfl_xor(__double2loint(m), o, 64);
+    const int hi = __shfl_xor(__double2hiint(m), o, 64);
+    const double y = __hiloint2double(hi, lo);
+    if (y > m) m = y;
+  }
+  return m;
+}
+
+// After the step's ticks, before the hand-off takes the step's flags. One
+// workgroup per swarm, a wave per vehicle (v = wave, wave + 4, ...), lane l
+// owns entries l and l + 64.
+//   1. a vehicle that adopted in this step's ticks publishes its assignment:
+//      its localization row becomes its auctioneer's (newAssignmentCb ->
+//      LocalizationROS::assignmentCb); nothing else writes loc_Pt;
+//   2. on a step that ran a gossip round, its localize status -> xst;
+//   3. kDiag: the estimate-error record of fleet_episode.hip's
+//      fleet_est_err_kernel in the same arithmetic (every maximum from +0.0,
+//      taken with >), except that err2_nbr runs over the vehicles whose
+//      controller runs in this step only: ctl_on, or an adoption in this step
+//      (the hand-off that follows sets exactly that bit).
+// A BAD_INPUT swarm and a finished trial return before anything is read.
+template <bool kDiag>
+__global__ void __launch_bounds__(kFleetLoopBlock) fleet_trial_est_post_kernel(const FtrPost A) {
+  __shared__ double q_s[3 * kFleetMaxN];
+  __shared__ unsigned long long adj_s[2 * kFleetMaxN];
+  __shared__ double d2_s[kFleetLoopBlock / 64][kFleetMaxN];
+  __shared__ double red_s[kFleetLoopBlock / 64][3];
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x, n = A.n;
+  if (A.skip[b] != 0 || A.fidx_eff[b] < 0) return;  // block-uniform
+  const int lane = tid & 63, wv = tid >> 6;
+  const size_t vb = (size_t)b * n;
+  for (int v = wv; v < n; v += kFleetLoopBlock / 64) {
+    if ((A.vf[vb + v] & ACL_FLEET_V_ADOPTED) == 0) continue;  // wave-uniform
+    const uint16_t* row = A.Pt + (vb + v) * n;
+    uint16_t* lrow = A.loc_Pt + (vb + v) * n;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int j = lane + 64 * s;
+      if (j < n) lrow[j] = row[j];
+    }
+  }
+  if (A.round != 0 && tid == 0) {
+    const acl_fleet_localize_status_t ls = A.lst[b];
+    acl_fleet_est_episode_status_t* x = A.xst + b;
+    x->rounds_run += ls.rounds_run;
+    x->n_unknown = ls.n_unknown;
+    x->max_age = ls.max_age;
+  }
+  if constexpr (!kDiag) return;
+  const int NW = (n + 63) >> 6;
+  {
+    const double* gq = A.q + vb * 3;
+    for (int k = tid; k < 3 * n; k += kFleetLoopBlock) q_s[k] = gq[k];
+    const uint64_t* ga = A.adj + (size_t)A.fidx_eff[b] * n * NW;  // (not skipped: fidx is valid)
+    for (int k = tid; k < n * NW; k += kFleetLoopBlock) adj_s[k] = ga[k];
+  }
+  __syncthreads();
+  double m_own = 0.0, m_nbr = 0.0, m_all = 0.0;
+  for (int v0 = 0; v0 < n; v0 += kFleetLoopBlock / 64) {  // block-uniform trip count
+    const int v = v0 + wv;
+    const bool act = v < n;
+    unsigned x[2] = {0xFFFFu, 0xFFFFu};
+    bool on = false;
+    if (act) {
+      const double* T = A.est + (vb + v) * n * 3;
+      const int32_t* st = A.stamp + (vb + v) * n;
+      const uint16_t* row = A.Pt + (vb + v) * n;
+      on = A.ctl_on[vb + v] != 0 || (A.vf[vb + v] & ACL_FLEET_V_ADOPTED) != 0;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int j = lane + 64 * s;
+        if (j < n) {
+          const double dx = T[3 * j] - q_s[3 * j];
+          const double dy = T[3 * j + 1] - q_s[3 * j + 1];
+          const double dz = T[3 * j + 2] - q_s[3 * j + 2];
+          const double d2 = (dx * dx + dy * dy) + dz * dz;
+          d2_s[wv][j] = d2;
+          if (j == v) {
+            if (d2 > m_own) m_own = d2;
+          } else if (st[j] != 0) {
+            if (d2 > m_all) m_all = d2;
+          }
+          x[s] = row[j];
+        }
+      }
+    }
+    __syncthreads();
+    if (act && on) {
+      // i: the vehicle's own point in its row
+      const unsigned long long own0 = __ballot(x[0] == (unsigned)v);
+      const unsigned long long own1 = __ballot(x[1] == (unsigned)v);
+      const int i = own0   ? __ffsll((long long)own0) - 1
+                    : own1 ? 63 + __ffsll((long long)own1)
+                           : -1;
+      if (i >= 0) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const int jj = lane + 64 * s;
+          if (jj < n && x[s] < (unsigned)n && ((adj_s[i * NW + s] >> lane) & 1ull)) {
+            const double d2 = d2_s[wv][x[s]];
+            if (d2 > m_nbr) m_nbr = d2;
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+  m_own = ftr_wave_max_gt(m_own);
+  m_nbr = ftr_wave_max_gt(m_nbr);
+  m_all = ftr_wave_max_gt(m_all);
+  if (lane == 0) {
+    red_s[wv][0] = m_own;
+    red_s[wv][1] = m_nbr;
+    red_s[wv][2] = m_all;
+  }
+  __syncthreads();
+  if (tid < 3) {
+    double m = red_s[0][tid];
+    for (int w = 1; w < kFleetLoopBlock / 64; ++w)
+      if (red_s[w][tid] > m) m = red_s[w][tid];
+    if (A.err2_hist) A.err2_hist[((size_t)A.k * A.B + b) * 3 + tid] = m;
+    acl_fleet_est_episode_status_t* x = A.xst + b;
+    double* acc = tid == 0 ? &x->err2_own : tid == 1 ? &x->err2_nbr : &x->err2_all;
+    if (m > *acc) *acc = m;
+  }
+}
+
+}  // namespace acl_amd
+
+namespace {
+
+acl_status_t ftr_est_init_launch(const acl_amd::FtrOwn& O, int n, int B, hipStream_t s) {
+  using namespace acl_amd;
+  hipLaunchKernelGGL(fleet_trial_est_init_kernel<FtrOwn>, dim3(B), dim3(kFleetLoopBlock), 0, s, O,
+                     n);
+  if (hipGetLastError() != hipSuccess)
+    return acl__set_error("fleet_trial_est_init_kernel launch failed");
+  return ACL_OK;
+}
+
+acl_status_t ftr_est_post_launch(const acl_amd::FtrPost& X, bool diag, hipStream_t s) {
+  using namespace acl_amd;
+  const dim3 grid(X.B), block(kFleetLoopBlock);
+  if (diag)
+    hipLaunchKernelGGL(fleet_trial_est_post_kernel<true>, grid, block, 0, s, X);
+  else
+    hipLaunchKernelGGL(fleet_trial_est_post_kernel<false>, grid, block, 0, s, X);
+  if (hipGetLastError() != hipSuccess)
+    return acl__set_error("fleet_trial_est_post_kernel launch failed");
+  return ACL_OK;
+}
+
+// the argument errors of the two own-estimate entries that need no pointer
+acl_status_t ftr_est_check(const acl_fleet_est_trial_args_t* x, int n, const char* who,
+                           FtrDelay* dl, acl_amd::FtrOwn* own) {
+  const acl_fleet_delay_trial_args_t* d = &x->lossy.delay;
+  acl_status_t r = ftr_check(&d->base, n, who);
+  if (r != ACL_OK) return r;
+  r = ftr_delay(d, who, dl);
+  if (r != ACL_OK) return r;
+  if (x->track_every < 1) return acl_amd::fleet_error(who, "track_every < 1");
+  dl->link = &x->lossy.link;
+  own->track_every = x->track_every; own->diag = x->diag;
+  own->loc_stamp = x->loc_stamp; own->loc_est = x->loc_est; own->loc_round = x->loc_round;
+  own->loc_n_lost = x->loc_n_lost; own->loc_Pt = x->loc_Pt; own->xst = x->xst;
+  own->err2_hist = x->err2_hist;
+  return ACL_OK;
+}
+
+}  // namespace
+
+extern "C" size_t acl_fleet_est_trial_workspace_bytes(int32_t n, int32_t B, int32_t queue_cap,
+                                                      int32_t max_lat) {
+  using namespace acl_amd;
+  if (n < 1 || n > kFleetMaxN || B < 1 || queue_cap < 1 || max_lat < 1 || max_lat > kFleetMaxLat)
+    return 0;
+  return ftr_layout(n, B, queue_cap, fleet_log_len(max_lat), true).total;
+}
+
+extern "C" acl_status_t acl_fleet_est_trial_init(const acl_fleet_est_trial_args_t* x, int32_t n,
+                                                 void* stream) {
+  static const char who[] = "acl_fleet_est_trial_init";
+  if (!x) return acl__set_error("acl_fleet_est_trial_init: null argument");
+  FtrDelay dl;
+  acl_amd::FtrOwn own;
+  const acl_status_t r = ftr_est_check(x, n, who, &dl, &own);
+  if (r != ACL_OK) return r;
+  dl.link = nullptr;  // (the init reads no loss matrix: acl_fleet_delay_trial_init on lossy.delay)
+  return ftr_init(who, &x->lossy.delay.base, n, dl, stream, &own);
+}
+
+extern "C" acl_status_t acl_fleet_est_trial_batch(const acl_formations_t* F,
+                                                  const acl_fleet_est_trial_args_t* x,
+                                                  void* stream) {
+  static const char who[] = "acl_fleet_est_trial_batch";
+  if (!F || !x) return acl__set_error("acl_fleet_est_trial_batch: null argument");
+  FtrDelay dl;
+  acl_amd::FtrOwn own;
+  const acl_status_t r = ftr_est_check(x, F->n, who, &dl, &own);
+  return r != ACL_OK ? r : ftr_run(who, F, &x->lossy.delay.base, dl, stream, &own);
 }

@@ -1615,17 +1615,8 @@ class FleetTrial(_LossyLinks):
         steps = int(steps)
         if steps < 0:
             raise ValueError(f"FleetTrial.run: steps = {steps} < 0")
-        dev, B, n = self.device, self.B, self.n
-        hist = None
-        if history:
-            def z(shape, dt):
-                return torch.zeros(shape, dtype=dt, device=dev)
-            hist = {"q": z((steps, B, n, 3), torch.float64),
-                    "vel": z((steps, B, n, 3), torch.float64),
-                    "u": z((steps, B, n, 3), torch.float64),
-                    "ca": z((steps, B, n), torch.uint8), "ctl": z((steps, B, n), torch.uint8),
-                    "P": z((steps, B, n), torch.int16), "state": z((steps, B), torch.int32),
-                    "vflags": z((steps, B, n), torch.int32)}
+        dev = self.device
+        hist = self._histories(steps) if history else None
         a = self._args(steps, hist)
         F = self.table.struct()
         if stream is None:
@@ -1644,6 +1635,19 @@ class FleetTrial(_LossyLinks):
         self.step += steps
         return hist
 
+    def _histories(self, steps):
+        """The zeroed history tensors of one run."""
+        dev, B, n = self.device, self.B, self.n
+
+        def z(shape, dt):
+            return torch.zeros(shape, dtype=dt, device=dev)
+        return {"q": z((steps, B, n, 3), torch.float64),
+                "vel": z((steps, B, n, 3), torch.float64),
+                "u": z((steps, B, n, 3), torch.float64),
+                "ca": z((steps, B, n), torch.uint8), "ctl": z((steps, B, n), torch.uint8),
+                "P": z((steps, B, n), torch.int16), "state": z((steps, B), torch.int32),
+                "vflags": z((steps, B, n), torch.int32)}
+
     def status(self):
         """Per-trial supervisor state and counters, structured numpy [B]."""
         arr = np.ascontiguousarray(self.ts.cpu().numpy())
@@ -1659,6 +1663,119 @@ class FleetTrial(_LossyLinks):
                 "ticks": view(self._status, L.FLEET_STATUS_DTYPE)}
 
     records = Trial.records
+
+
+class FleetEstTrial(FleetTrial):
+    """Monte-Carlo trials on each vehicle's own estimates
+    (acl_fleet_est_trial_init / acl_fleet_est_trial_batch, added within ABI
+    11): FleetTrial in which no vehicle reads the shared snapshot q. Every
+    track_every control steps (default 2) the vehicles run one gossip round of
+    FleetLocalization's model on the true q, subscribed under their
+    localization rows loc_Pt (the assignment a vehicle last published: a
+    formation change does not touch it); a START aligns and prices on the
+    vehicle's own table, and the vehicle steers and avoids on it.
+    include/aclswarm_amd.h states the model and its limits.
+
+    The arguments are FleetTrial's. The object always runs the new entry:
+    latency None means every link at 1 tick, loss None means loss 0 on every
+    link with seed 0 (tables are lost under the same loss and loss_seed as the
+    bids). It also owns loc_stamp [B][n][n] i32, loc_est [B][n][n][3] f64,
+    loc_round [B] i32, loc_n_lost [B][n] i32 (lost tables; n_lost stays the
+    bids'), loc_Pt [B][n][n] int16 and xst, the acl_fleet_est_episode_status_t
+    records, all set by acl_fleet_est_trial_init. diag=True also records, per
+    step, how wrong the tables are against the true q (the err2 maxima of the
+    header, m^2). Raises ValueError on a malformed argument before anything
+    runs."""
+
+    LOC_KEYS = ("loc_stamp", "loc_est", "loc_round", "loc_n_lost", "loc_Pt", "xst")
+
+    def __init__(self, table, fseq, q, vel, params=None, cntrl=None, safety=None, queue_cap=None,
+                 max_iter=0, ticks_per_step=10, latency=None, max_latency=None, loss=None,
+                 loss_seed=None, track_every=2, diag=False):
+        self._check_track_every("FleetEstTrial", track_every)
+        if loss is None and loss_seed is not None:
+            raise ValueError("FleetEstTrial: loss_seed is given without loss")
+        self.track_every, self.diag = int(track_every), bool(diag)
+        super().__init__(table, fseq, q, vel, params=params, cntrl=cntrl, safety=safety,
+                         queue_cap=queue_cap, max_iter=max_iter, ticks_per_step=ticks_per_step,
+                         latency=1 if latency is None else latency, max_latency=max_latency,
+                         loss=0 if loss is None else loss, loss_seed=loss_seed)
+        B, n, dev = self.B, self.n, self.device
+        self.loc_stamp = torch.empty((B, n, n), dtype=torch.int32, device=dev)
+        self.loc_est = torch.empty((B, n, n, 3), dtype=torch.float64, device=dev)
+        self.loc_round = torch.empty((B,), dtype=torch.int32, device=dev)
+        self.loc_n_lost = torch.empty((B, n), dtype=torch.int32, device=dev)
+        self.loc_Pt = torch.empty((B, n, n), dtype=torch.int16, device=dev)
+        self.xst = torch.empty((B, L.FLEET_EST_EPISODE_STATUS_DTYPE.itemsize), dtype=torch.uint8,
+                               device=dev)
+        # (the base class ran the delay entry's init; this one repeats it and
+        # sets the own-estimate arrays and the workspace tail)
+        x = self._est_args(0)
+        stream = ct.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        L.check(L.lib().acl_fleet_est_trial_init(ct.byref(x), n, stream),
+                "acl_fleet_est_trial_init")
+
+    @staticmethod
+    def _check_track_every(what, track_every):
+        if isinstance(track_every, bool) or not isinstance(track_every, (int, np.integer)) or \
+                track_every < 1:
+            raise ValueError(f"{what}: track_every = {track_every!r} must be an int >= 1")
+
+    def workspace_bytes(self):
+        return int(L.lib().acl_fleet_est_trial_workspace_bytes(
+            self.n, self.B, self.queue_cap, self.max_latency))
+
+    def _est_args(self, steps, hist=None):
+        """FleetEstTrialArgs around FleetTrial._args's FleetLossyTrialArgs."""
+        x = L.FleetEstTrialArgs()
+        err2 = hist.pop("err2", None) if hist is not None else None
+        x.lossy = self._args(steps, hist)
+        x.track_every, x.diag = int(self.track_every), 1 if self.diag else 0
+        for k in self.LOC_KEYS:
+            setattr(x, k, getattr(self, k).data_ptr())
+        if err2 is not None:
+            hist["err2"] = err2
+            x.err2_hist = err2.data_ptr()
+        return x
+
+    def run(self, steps, history=False, stream=None, own_estimates=True):
+        """FleetTrial.run; with history=True and diag set the dict also holds
+        "err2" [steps][B][3] f64 (own, nbr, all; rows of BAD_INPUT swarms and
+        finished trials stay 0). own_estimates=False flies the steps on
+        acl_fleet_lossy_trial_batch instead (the shared snapshot q; the
+        trackers and loc_Pt stand still): a trial may move between the two
+        entries from run to run."""
+        if not own_estimates:
+            return super().run(steps, history=history, stream=stream)
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError(f"FleetEstTrial.run: steps = {steps} < 0")
+        self._check_track_every("FleetEstTrial.run", self.track_every)
+        if self._loss is None:
+            raise ValueError("FleetEstTrial.run: loss is None; the entry takes a loss matrix "
+                             "(0 on every link: no loss)")
+        dev = self.device
+        hist = self._histories(steps) if history else None
+        if history and self.diag:
+            hist["err2"] = torch.zeros((steps, self.B, 3), dtype=torch.float64, device=dev)
+        x = self._est_args(steps, hist)
+        F = self.table.struct()
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        L.check(L.lib().acl_fleet_est_trial_batch(ct.byref(F), ct.byref(x), ct.c_void_p(stream)),
+                "acl_fleet_est_trial_batch")
+        self.step += steps
+        return hist
+
+    def fleet_status(self):
+        """FleetTrial.fleet_status with "estimates": the
+        acl_fleet_est_episode_status_t records (rounds_run, n_unknown, max_age,
+        flags, err2_own, err2_nbr, err2_all). status() stays the supervisor's
+        records, as for every trial."""
+        st = super().fleet_status()
+        st["estimates"] = np.ascontiguousarray(self.xst.cpu().numpy()).view(
+            L.FLEET_EST_EPISODE_STATUS_DTYPE).reshape(-1)
+        return st
 
 
 def generate_formation_groups(seeds, n, fc, l, w, h, min_dist=2.0, max_candidates=0,

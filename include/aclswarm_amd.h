@@ -876,10 +876,11 @@ acl_status_t acl_fleet_lossy_auction_batch(const acl_formations_t* formations,
  * NULL adj / fidx / Pt / stamp / est / round / status, q NULL with rounds > 0.
  * Stream-ordered, never synchronises.
  *
- * Not modelled: trials from own estimates (the auction's START, one control
- * step and the episodes of acl_fleet_est_episode_batch read them, below);
- * gossip latency of whole rounds; outages of a vehicle's own state feed;
- * n > 128; the reference's "make this smarter using Dijkstra's" TODO. */
+ * Not modelled (the auction's START, one control step, the episodes of
+ * acl_fleet_est_episode_batch and the trials of acl_fleet_est_trial_batch read
+ * the tables, below): gossip latency of whole rounds; outages of a vehicle's
+ * own state feed; n > 128; the reference's "make this smarter using
+ * Dijkstra's" TODO. */
 #define ACL_FLEET_LOC_BAD_ROW 0x8 /* localize status.flags: a row is no permutation */
 
 typedef struct {
@@ -925,10 +926,9 @@ acl_status_t acl_fleet_localize_batch(const acl_formations_t* formations,
  * and q is NULL"), plus est NULL with cmd. Added symbols: ACL_ABI_VERSION
  * stays 11.
  *
- * Not modelled: as for acl_fleet_localize_batch -- the trials still read one
- * shared snapshot (one control step from own estimates is
- * acl_fleet_est_control_batch, the closed loop acl_fleet_est_episode_batch,
- * below). */
+ * Not modelled: as for acl_fleet_localize_batch (one control step from own
+ * estimates is acl_fleet_est_control_batch, the closed loops
+ * acl_fleet_est_episode_batch and acl_fleet_est_trial_batch, below). */
 typedef struct {
   acl_fleet_lossy_args_t lossy; /* lossy.delay.base.q is ignored */
   const double* est;            /* [B][n][n][3]: est[b][v] is vehicle v's snapshot */
@@ -988,9 +988,8 @@ acl_status_t acl_fleet_est_auction_batch(const acl_formations_t* formations,
  * u_safe / ca_flag / status. No workspace. Stream-ordered, never synchronises,
  * no global counters.
  *
- * Not modelled: trials on own estimates (they still read one shared snapshot;
- * the closed loop of the episodes is acl_fleet_est_episode_batch); what
- * acl_fleet_localize_batch does not model. */
+ * Not modelled: what acl_fleet_localize_batch does not model (the closed loops
+ * are acl_fleet_est_episode_batch and acl_fleet_est_trial_batch). */
 #define ACL_FLEET_CTL_BAD_ROW 0x8 /* control status.flags: a row is no permutation */
 
 typedef struct {
@@ -1447,9 +1446,9 @@ acl_status_t acl_fleet_lossy_episode_batch(const acl_formations_t* formations,
  * On a complete graph with track_every = 1 and no loss every table is q bit
  * for bit after the step's round, and this is acl_fleet_lossy_episode_batch
  * step for step, the control step's sum order apart.
- * Not modelled: trials from own estimates; a loss matrix of its own for
- * tables; gossip latency of whole rounds; outages of a vehicle's own state
- * feed; n > 128. */
+ * Not modelled: a loss matrix of its own for tables (the trials on own
+ * estimates are acl_fleet_est_trial_batch, below); gossip latency of whole
+ * rounds; outages of a vehicle's own state feed; n > 128. */
 typedef struct {
   int32_t rounds_run;   /* gossip rounds, accumulated */
   int32_t n_unknown;    /* entries with stamp 0 after the last round run */
@@ -1840,6 +1839,123 @@ typedef struct {
 
 acl_status_t acl_fleet_lossy_trial_batch(const acl_formations_t* formations,
                                          const acl_fleet_lossy_trial_args_t* args, void* stream);
+
+/* ---- the trials on each vehicle's own estimates (added within ABI 11) -------
+ * acl_fleet_est_trial_batch is acl_fleet_lossy_trial_batch in which no vehicle
+ * reads the shared snapshot q[b]: the closed loop of acl_fleet_localize_batch,
+ * acl_fleet_est_auction_batch and acl_fleet_est_control_batch under the
+ * supervisor and the formation sequence of the trials. Added symbols:
+ * ACL_ABI_VERSION stays 11 (no existing struct or call changed).
+ *
+ * The localization row. At a formation change the reference's localization
+ * node and its auctioneer disagree about the vehicle's neighbours.
+ * Auctioneer::setFormation resets the auctioneer's assignment to the identity
+ * (auctioneer.cpp:42-62) and the bid subscriptions are rebuilt from it
+ * (coordination_ros.cpp:129-134). LocalizationROS::formationCb only replaces
+ * adjmat_ (localization_ros.cpp:77-85): its P_ stays the last assignment the
+ * vehicle's coordination node PUBLISHED (assignmentCb :89-97, fed by
+ * newAssignmentCb, coordination_ros.cpp:293-297), and nothing publishes at a
+ * commit. Between a commit and the vehicle's first adoption in the new
+ * formation its tables therefore arrive over (new graph, old assignment) while
+ * its bids arrive over (new graph, identity). loc_Pt[b][v] is that row:
+ * vehicle v's LOCALIZATION row, formation point -> vehicle, beside its
+ * auctioneer's row Pt[b][v].
+ *
+ * Per global step s = step0 + k, for every swarm neither finished nor flagged
+ * ACL_FLEET_BAD_INPUT; everything not listed (supervisor, countdown, records,
+ * hand-off, the commit on the delay layout) is acl_fleet_lossy_trial_batch's,
+ * step for step:
+ *   1. commit and commands: steps 1 and 2 of acl_fleet_trial_batch. The commit
+ *      does NOT touch loc_Pt, loc_stamp, loc_est or loc_round: the trackers
+ *      and the localization rows survive a formation change;
+ *   2. gossip: if s % track_every == 0, one round of acl_fleet_localize_batch
+ *      AFTER this step's commit -- the adjacency is that of the formation the
+ *      swarm flies from this step on (formationCb acts on the message, not on
+ *      the 5 Hz spin) -- with subscriptions under loc_Pt, not Pt, sensing the
+ *      true q[b] as it stands at the start of the step. Tables are lost under
+ *      link.loss / link.seed with loc_round[b] as the publication word, and
+ *      counted in loc_n_lost (link.n_lost stays the bids'). A finished trial is
+ *      handed over with formation -1: its trackers do not move;
+ *   3. ticks: ticks_per_step ticks of acl_fleet_est_auction_batch; a START of
+ *      vehicle v reads loc_est[b][v];
+ *   4. hand-off: step 4 of acl_fleet_trial_batch. In addition a vehicle that
+ *      raised ACL_FLEET_V_ADOPTED during this step's ticks publishes its
+ *      assignment: loc_Pt[b][v][:] = Pt[b][v][:]. That is the only write to
+ *      loc_Pt after init; this step's round has run, so the new row acts from
+ *      the next round on;
+ *   5. control: acl_fleet_est_control_batch on (loc_est, vel, Pt after this
+ *      step's ticks) into the trial's u / u_safe / ca scratch. ctl_on gates
+ *      what the trajectory and the supervisor read, as in every trial. While
+ *      ctl_on[b][v] is set Pt[b][v] is the row the controller flies: a row
+ *      changes only by an adoption, which hands it over in the same step, or
+ *      by a commit, which stops the controller;
+ *   6. record: on a step that ran a round its localize status goes into xst
+ *      (rounds_run accumulates, n_unknown and max_age are overwritten). With
+ *      diag != 0 the three maxima of acl_fleet_est_episode_batch's step 5, in
+ *      the same arithmetic (one IEEE operation each, from +0.0, taken with >),
+ *      with one sentence changed: err2_nbr runs over the vehicles with
+ *      ctl_on != 0 (after this step's hand-off) only -- a stopped controller
+ *      reads nothing; err2_own and err2_all run over every vehicle. A finished
+ *      or skipped trial writes neither xst nor its err2_hist row;
+ *   7. trajectories and supervisor tick on the true q: steps 3 and 4 of
+ *      acl_trial_batch.
+ * u_hist / ca_hist hold what the trajectory read: for a finished trial, as for
+ * every stopped controller, zeros. (acl_fleet_est_control_batch zeroes the
+ * scratch commands of a swarm with formation -1, where the shared-snapshot
+ * control stage leaves the scratch alone; nothing downstream reads either.)
+ *
+ * acl_fleet_est_trial_init is acl_fleet_delay_trial_init on lossy.delay, plus:
+ * identity rows in loc_Pt; loc_stamp, loc_est, loc_round, loc_n_lost and xst
+ * zeroed; the workspace tail zeroed.
+ *
+ * Workspace: acl_fleet_est_trial_workspace_bytes(n, B, queue_cap, max_lat)
+ * bytes: the layout of acl_fleet_delay_trial_workspace_bytes with the status
+ * arrays of the localize and control entries appended; nothing before them
+ * moves. On a workspace of this size a trial may move between
+ * acl_fleet_delay_trial_batch, acl_fleet_lossy_trial_batch and this entry from
+ * call to call. Under the other two the trackers and loc_Pt stand still: an
+ * adoption made there does NOT reach loc_Pt.
+ *
+ * Argument errors, reported before any HIP call: those of
+ * acl_fleet_lossy_trial_batch on `lossy`; track_every < 1; with B > 0 and
+ * steps > 0 a NULL loc_stamp, loc_est, loc_round, loc_n_lost, loc_Pt or xst;
+ * workspace_bytes too small (acl_fleet_est_trial_workspace_bytes). Not
+ * argument errors: a loc_Pt row that is not a permutation -- that vehicle
+ * receives no tables, as acl_fleet_localize_batch states; a swarm flagged
+ * ACL_FLEET_BAD_INPUT at the call's first hand-off is untouched in every
+ * respect, loc_stamp / loc_est / loc_round / loc_n_lost / loc_Pt / xst and its
+ * err2_hist rows included.
+ *
+ * Reductions: (a) with K = 1 (no formation change after the first commit,
+ * before which every row is the identity) loc_Pt equals Pt at every step and
+ * the localization part is acl_fleet_est_episode_batch's; (b) on complete
+ * graphs with track_every = 1 and loss 0 every table is q bit for bit after
+ * the round, and this is acl_fleet_lossy_trial_batch step for step, the
+ * control step's sum order apart.
+ *
+ * Model limits: those of acl_fleet_lossy_trial_batch and of
+ * acl_fleet_est_episode_batch; the vehicle's published assignment reaches its
+ * own localization node in the step of the adoption; gossip latency below one
+ * round. Not modelled: outages of a vehicle's own state feed; n > 128. */
+typedef struct {
+  acl_fleet_lossy_trial_args_t lossy; /* delay.base.q: the true positions */
+  int32_t track_every;   /* >= 1 */
+  int32_t diag;          /* != 0: the error record runs */
+  int32_t* loc_stamp;    /* [B][n][n]     acl_fleet_localize_args_t's, in/out */
+  double*  loc_est;      /* [B][n][n][3] */
+  int32_t* loc_round;    /* [B] */
+  int32_t* loc_n_lost;   /* [B][n] lost tables; lossy.link.n_lost stays the bids' */
+  uint16_t* loc_Pt;      /* [B][n][n] in/out: vehicle v's LOCALIZATION row, above */
+  acl_fleet_est_episode_status_t* xst; /* [B] in/out */
+  double*  err2_hist;    /* [steps][B][3] or NULL (read only with diag) */
+} acl_fleet_est_trial_args_t;
+
+size_t acl_fleet_est_trial_workspace_bytes(int32_t n, int32_t B, int32_t queue_cap,
+                                           int32_t max_lat);
+acl_status_t acl_fleet_est_trial_init(const acl_fleet_est_trial_args_t* args, int32_t n,
+                                      void* stream);
+acl_status_t acl_fleet_est_trial_batch(const acl_formations_t* formations,
+                                       const acl_fleet_est_trial_args_t* args, void* stream);
 
 /* ---- random formation groups on the device -----------
  * Replaces aclswarm_sim/nodes/generate_random_formation.py:59-80

@@ -46,6 +46,8 @@ EXPORTS = (
     "acl_fleet_lossy_auction_batch", "acl_fleet_lossy_episode_batch",
     "acl_fleet_lossy_trial_batch",
     "acl_fleet_localize_batch", "acl_fleet_est_auction_batch", "acl_fleet_est_control_batch",
+    "acl_fleet_delay_localize_workspace_bytes", "acl_fleet_delay_localize_batch",
+    "acl_fleet_delay_est_episode_batch",
     "acl_fleet_est_episode_workspace_bytes", "acl_fleet_est_episode_batch",
     "acl_fleet_est_trial_workspace_bytes", "acl_fleet_est_trial_init",
     "acl_fleet_est_trial_batch",
@@ -181,6 +183,14 @@ class FleetLocalizeArgs(ct.Structure):
                                    "n_lost", "status")]
 
 
+class FleetDelayLocalizeArgs(ct.Structure):
+    """acl_fleet_delay_localize_args_t (added within ABI 11): fleet localization
+    with table latency in whole rounds and outages of the own state feed."""
+    _fields_ = [("base", FleetLocalizeArgs), ("tlat", ct.c_void_p), ("max_tlat", ct.c_int32),
+                ("feed_loss", ct.c_void_p), ("n_missed", ct.c_void_p),
+                ("workspace", ct.c_void_p), ("workspace_bytes", ct.c_size_t)]
+
+
 class FleetEstArgs(ct.Structure):
     """acl_fleet_est_args_t (added within ABI 11): the lossy fleet auction whose
     START reads vehicle v's own snapshot est[b][v]."""
@@ -272,6 +282,14 @@ class FleetEstEpisodeArgs(ct.Structure):
                 ("diag", ct.c_int32)] + [
         (n, ct.c_void_p) for n in ("loc_stamp", "loc_est", "loc_round", "loc_n_lost", "xst",
                                    "err2_hist")]
+
+
+class FleetDelayEstEpisodeArgs(ct.Structure):
+    """acl_fleet_delay_est_episode_args_t (added within ABI 11): the episodes on
+    own estimates whose gossip round is acl_fleet_delay_localize_batch's."""
+    _fields_ = [("est", FleetEstEpisodeArgs), ("tlat", ct.c_void_p), ("max_tlat", ct.c_int32),
+                ("feed_loss", ct.c_void_p), ("loc_n_missed", ct.c_void_p),
+                ("loc_workspace", ct.c_void_p), ("loc_workspace_bytes", ct.c_size_t)]
 
 
 class FleetEstEpisodeStatus(ct.Structure):
@@ -491,6 +509,12 @@ def lib():
     for fn, args in (("acl_fleet_localize_batch", FleetLocalizeArgs),
                      ("acl_fleet_est_auction_batch", FleetEstArgs),
                      ("acl_fleet_est_control_batch", FleetEstControlArgs)):
+        getattr(L, fn).argtypes = [ct.POINTER(Formations), ct.POINTER(args), VP]
+        getattr(L, fn).restype = ct.c_int
+    L.acl_fleet_delay_localize_workspace_bytes.argtypes = [I32, I32, I32]
+    L.acl_fleet_delay_localize_workspace_bytes.restype = SZ
+    for fn, args in (("acl_fleet_delay_localize_batch", FleetDelayLocalizeArgs),
+                     ("acl_fleet_delay_est_episode_batch", FleetDelayEstEpisodeArgs)):
         getattr(L, fn).argtypes = [ct.POINTER(Formations), ct.POINTER(args), VP]
         getattr(L, fn).restype = ct.c_int
     L.acl_fleet_est_episode_workspace_bytes.argtypes = [I32, I32, I32, I32]

@@ -55,6 +55,9 @@
 //   fleet_est_err_kernel    the round's localize status -> xst's integers;
 //                           <true> (diag != 0): how wrong the tables are
 //                           against the true q
+// acl_fleet_delay_est_episode_batch is that loop with the gossip round
+// acl_fleet_delay_localize_batch's (FepOwn::dl): table latency in whole rounds
+// and feed outages, the publication log in a workspace of its own.
 #include "common.h"
 #include "episode_dev.h"
 #include "fleet_loop_dev.h"
@@ -145,6 +148,9 @@ struct FepOwn {
   int32_t* loc_n_lost;
   acl_fleet_est_episode_status_t* xst;
   double* err2_hist;
+  // acl_fleet_delay_est_episode_batch: the round is acl_fleet_delay_localize_batch's
+  // under these (base is filled by the loop); NULL: acl_fleet_localize_batch's
+  const acl_fleet_delay_est_episode_args_t* dl = nullptr;
 };
 
 struct EstErrArgs {
@@ -333,6 +339,10 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
   if (delay && (max_lat < 1 || max_lat > kFleetMaxLat)) return fail("max_lat out of range [1, 64]");
   if (!delay) max_lat = 0;
   if (own && own->track_every < 1) return fail("track_every < 1");
+  const acl_fleet_delay_est_episode_args_t* dl = own ? own->dl : nullptr;
+  if (dl && (dl->max_tlat < 0 || dl->max_tlat > 7)) return fail("max_tlat out of range [0, 7]");
+  if (dl && dl->feed_loss && !dl->loc_n_missed)
+    return fail("feed_loss is given and loc_n_missed is NULL");
   if (B == 0 || a->steps == 0) return ACL_OK;
   if (!a->fidx || !a->q || !a->vel || !a->P || !a->Pt || !a->open || !a->invalid ||
       !a->just_received || !a->biditer || !a->price || !a->who || !a->Rt || !a->final_price ||
@@ -347,6 +357,10 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
   if (own && (!own->loc_stamp || !own->loc_est || !own->loc_round || !own->loc_n_lost ||
               !own->xst))
     return fail("loc_stamp, loc_est, loc_round, loc_n_lost or xst is NULL");
+  if (dl && !dl->tlat) return fail("tlat is NULL");
+  if (dl && !dl->loc_workspace) return fail("loc_workspace is NULL");
+  if (dl && dl->loc_workspace_bytes < acl_fleet_delay_localize_workspace_bytes(n, B, dl->max_tlat))
+    return fail("loc_workspace_bytes is too small (acl_fleet_delay_localize_workspace_bytes)");
   const FepLayout W = fep_layout(n, B, a->queue_cap, max_lat, own != nullptr);
   if (a->workspace_bytes < W.total)
     return fail(own     ? "workspace_bytes is too small (acl_fleet_est_episode_workspace_bytes)"
@@ -384,7 +398,8 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
   cs.workspace = wc; cs.cntrl = a->cntrl; cs.safety = a->safety;
 
   // the loop on own estimates: the three public entries' arguments
-  acl_fleet_localize_args_t lo = {};
+  acl_fleet_delay_localize_args_t dlo = {};
+  acl_fleet_localize_args_t& lo = dlo.base;
   acl_fleet_est_control_args_t ec = {};
   EstErrArgs X = {};
   if (own) {
@@ -393,6 +408,11 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
     lo.B = B; lo.rounds = 1; lo.q_rounds = 1; lo.fidx = fidx_eff; lo.Pt = a->Pt; lo.q = a->q;
     lo.stamp = own->loc_stamp; lo.est = own->loc_est; lo.round = own->loc_round;
     lo.loss = link->loss; lo.seed = link->seed; lo.n_lost = own->loc_n_lost; lo.status = lst;
+    if (dl) {
+      dlo.tlat = dl->tlat; dlo.max_tlat = dl->max_tlat; dlo.feed_loss = dl->feed_loss;
+      dlo.n_missed = dl->loc_n_missed; dlo.workspace = dl->loc_workspace;
+      dlo.workspace_bytes = dl->loc_workspace_bytes;
+    }
     ec.B = B; ec.fidx = fidx_eff; ec.est = own->loc_est; ec.vel = a->vel; ec.Pt = a->Pt;
     ec.u = u; ec.u_safe = us; ec.ca_flag = ca;
     ec.status = reinterpret_cast<acl_fleet_control_status_t*>(ws + W.ecs);
@@ -433,7 +453,8 @@ acl_status_t fep_run(const char* who, bool delay, const acl_formations_t* F,
     const bool round = own && step % own->track_every == 0;
     if (round) {
       // the round senses q as it stands at the start of the step
-      const acl_status_t r = acl_fleet_localize_batch(F, &lo, stream);
+      const acl_status_t r = dl ? acl_fleet_delay_localize_batch(F, &dlo, stream)
+                                : acl_fleet_localize_batch(F, &lo, stream);
       if (r != ACL_OK) return r;
     }
     if (auction) {
@@ -508,5 +529,19 @@ extern "C" acl_status_t acl_fleet_est_episode_batch(const acl_formations_t* F,
   own.loc_stamp = x->loc_stamp; own.loc_est = x->loc_est; own.loc_round = x->loc_round;
   own.loc_n_lost = x->loc_n_lost; own.xst = x->xst; own.err2_hist = x->err2_hist;
   return fep_run("acl_fleet_est_episode_batch", true, F, &d->base, d->lat, d->max_lat,
+                 &x->lossy.link, stream, &own);
+}
+
+extern "C" acl_status_t acl_fleet_delay_est_episode_batch(
+    const acl_formations_t* F, const acl_fleet_delay_est_episode_args_t* y, void* stream) {
+  if (!y) return acl__set_error("acl_fleet_delay_est_episode_batch: null argument");
+  const acl_fleet_est_episode_args_t* x = &y->est;
+  const acl_fleet_delay_episode_args_t* d = &x->lossy.delay;
+  acl_amd::FepOwn own;
+  own.track_every = x->track_every; own.diag = x->diag;
+  own.loc_stamp = x->loc_stamp; own.loc_est = x->loc_est; own.loc_round = x->loc_round;
+  own.loc_n_lost = x->loc_n_lost; own.xst = x->xst; own.err2_hist = x->err2_hist;
+  own.dl = y;
+  return fep_run("acl_fleet_delay_est_episode_batch", true, F, &d->base, d->lat, d->max_lat,
                  &x->lossy.link, stream, &own);
 }

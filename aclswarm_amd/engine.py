@@ -544,6 +544,77 @@ class _LossyLinks:
         link.n_lost = self.n_lost.data_ptr()
 
 
+class _TableLinks:
+    """table_latency / max_table_latency / feed_loss of FleetLocalization and
+    FleetEstEpisode (acl_fleet_delay_localize_batch; include/aclswarm_amd.h
+    states the rule). table_latency: an int in 0..7 for every link, or a
+    contiguous uint8 tensor [B][n][n], receiver-major, in whole rounds; it is
+    copied, as feed_loss is. max_table_latency: 0..7, fixed for the object's
+    life (it sizes the publication log); default: the int, or 7 for a tensor.
+    feed_loss: an int in 0..65535 for every vehicle, or a uint16 / int16
+    (uint16 bits) tensor [B][n]. With none of the three the object runs the
+    entry without them; with any it owns the log workspace (zero-filled at
+    the first run) and n_missed [B][n] i32, the senses skipped per vehicle."""
+
+    MAX_TABLE_LATENCY = 7
+    table_latency = None
+    max_table_latency = None
+    feed_loss = None
+    n_missed = None
+    loc_ws = None
+    _feed_seed = None
+
+    def _table_setup(self, what, table_latency, max_table_latency, feed_loss, B, n, dev):
+        """(constructor) the checked copies, before anything is allocated or run."""
+        if table_latency is None and max_table_latency is None and feed_loss is None:
+            return
+        top = self.MAX_TABLE_LATENCY
+        mx = max_table_latency
+        if mx is not None and (not _LossyLinks._is_int(mx) or not 0 <= int(mx) <= top):
+            raise ValueError(f"{what}: max_table_latency = {mx!r} must be an int in [0, {top}]")
+        tl = 0 if table_latency is None else table_latency
+        if _LossyLinks._is_int(tl):
+            if not 0 <= int(tl) <= top:
+                raise ValueError(f"{what}: table_latency = {tl} out of range [0, {top}]")
+            if mx is None:
+                mx = int(tl)
+            if int(tl) > int(mx):
+                raise ValueError(f"{what}: table_latency = {tl} > max_table_latency = {mx}")
+            tlat = torch.full((B, n, n), int(tl), dtype=torch.uint8, device=dev)
+        else:
+            FleetAuction._check(what, {"table_latency": (tl, (torch.uint8,), (B, n, n))}, dev)
+            tlat = tl.clone()
+            if mx is None:
+                mx = top
+        fl = 0 if feed_loss is None else feed_loss
+        if _LossyLinks._is_int(fl):
+            if not 0 <= int(fl) <= 0xFFFF:
+                raise ValueError(f"{what}: feed_loss = {fl} out of range [0, 65535]")
+            bits = int(fl) - 0x10000 if int(fl) >= 0x8000 else int(fl)
+            feed = torch.full((B, n), bits, dtype=torch.int16, device=dev)
+        else:
+            dts = tuple(d for d in (getattr(torch, "uint16", None), torch.int16) if d is not None)
+            FleetAuction._check(what, {"feed_loss": (fl, dts, (B, n))}, dev)
+            feed = fl.clone()
+        self.table_latency, self.max_table_latency, self.feed_loss = tlat, int(mx), feed
+        self.n_missed = torch.zeros((B, n), dtype=torch.int32, device=dev)
+
+    def _table_args(self, what, d, n_missed_key="n_missed", ws_key="workspace"):
+        """Fills the fields an acl_fleet_delay_*_args_t adds; allocates the log."""
+        B, n, dev = self.B, self.n, self.device
+        FleetAuction._check(what, {"table_latency": (self.table_latency, (torch.uint8,), (B, n, n))},
+                            dev)
+        if self.loc_ws is None:
+            nbytes = int(L.lib().acl_fleet_delay_localize_workspace_bytes(
+                n, B, self.max_table_latency))
+            self.loc_ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        d.tlat, d.max_tlat = self.table_latency.data_ptr(), self.max_table_latency
+        d.feed_loss = self.feed_loss.data_ptr()
+        setattr(d, n_missed_key, self.n_missed.data_ptr())
+        setattr(d, ws_key, self.loc_ws.data_ptr())
+        setattr(d, ws_key + "_bytes", self.loc_ws.numel())
+
+
 class FleetAuction(_LossyLinks):
     """acl_fleet_auction_batch (added within ABI 11): the message-level CBAA of
     B swarms of n vehicles -- every vehicle an Auctioneer of the reference
@@ -772,7 +843,7 @@ class FleetAuction(_LossyLinks):
         return arr.view(L.FLEET_STATUS_DTYPE).reshape(-1)
 
 
-class FleetLocalization(_LossyLinks):
+class FleetLocalization(_LossyLinks, _TableLinks):
     """acl_fleet_localize_batch (added within ABI 11): B swarms of n <= 128
     VehicleTrackers (localization_ros.cpp, vehicle_tracker.cpp) advanced round
     by round on the device, one launch per run(). A round is one tracking_dt
@@ -787,12 +858,18 @@ class FleetLocalization(_LossyLinks):
     loss / loss_seed as _LossyLinks takes them (a table on link u -> w is lost
     by the hash of (seed, w, u, round, 0xFFFFFFFF)). The object owns est
     [B][n][n][3] f64, stamp [B][n][n] i32, round [B] i32, n_lost and the
-    status; all zero: freshly constructed trackers. Raises ValueError on a
-    malformed argument before anything runs."""
+    status; all zero: freshly constructed trackers.
+    table_latency / max_table_latency / feed_loss as _TableLinks takes them:
+    with any of them run() calls acl_fleet_delay_localize_batch (tables arrive
+    whole rounds late, a vehicle's own feed drops out by the hash of (seed, w,
+    w, round, 0xFFFFFFFE); without loss the seeds are loss_seed's, default 0),
+    with none of them the existing entry exactly as before. Raises ValueError
+    on a malformed argument before anything runs."""
 
     latency = 1  # (_LossyLinks: loss may be set on any object)
 
-    def __init__(self, table, fidx, Pt=None, loss=None, loss_seed=None):
+    def __init__(self, table, fidx, Pt=None, loss=None, loss_seed=None, table_latency=None,
+                 max_table_latency=None, feed_loss=None):
         what = "FleetLocalization"
         n = table.n
         if n < 1 or n > L.FLEET_MAX_N:
@@ -807,10 +884,13 @@ class FleetLocalization(_LossyLinks):
         FleetAuction._check(what, want, dev)
         if B < 1:
             raise ValueError(f"{what}: fidx is empty")
-        if loss is None and loss_seed is not None:
+        if loss is None and loss_seed is not None and feed_loss is None:
             raise ValueError(f"{what}: loss_seed is given without loss")
         self.table, self.fidx, self.n, self.B, self.device = table, fidx, n, B, dev
+        self._table_setup(what, table_latency, max_table_latency, feed_loss, B, n, dev)
         self._loss_setup(what, loss, loss_seed, B, n, dev)
+        if self.table_latency is not None and loss is None:  # the feed's seeds
+            self._feed_seed = self._seed_tensor(what, 0 if loss_seed is None else loss_seed, B, dev)
         if Pt is None:
             Pt = torch.arange(n, dtype=torch.int16, device=dev).repeat(B, n, 1)
         self.Pt = Pt
@@ -834,7 +914,9 @@ class FleetLocalization(_LossyLinks):
         FleetAuction._check(what, {"q": (q, (torch.float64,), shape)}, dev)
         if dev.type != "cuda":
             raise ValueError(f"{what}: the tensors must be on a CUDA device, not {dev}")
-        a = L.FleetLocalizeArgs()
+        delayed = self.table_latency is not None
+        d = L.FleetDelayLocalizeArgs() if delayed else None
+        a = d.base if delayed else L.FleetLocalizeArgs()
         a.B, a.rounds, a.q_rounds = B, rounds, 1 if q.dim() == 3 else rounds
         a.fidx, a.Pt, a.q = self.fidx.data_ptr(), self.Pt.data_ptr(), q.data_ptr()
         a.stamp, a.est, a.round = self.stamp.data_ptr(), self.est.data_ptr(), self.round.data_ptr()
@@ -842,9 +924,18 @@ class FleetLocalization(_LossyLinks):
             a.loss, a.seed = self._loss.data_ptr(), self._loss_seed.data_ptr()
             a.n_lost = self.n_lost.data_ptr()
         a.status = self._status.data_ptr()
+        if delayed:
+            self._table_args(what, d)
+            if self._loss is None:
+                a.seed = self._feed_seed.data_ptr()
         F = self.table.struct()
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
+        if delayed:
+            L.check(L.lib().acl_fleet_delay_localize_batch(ct.byref(F), ct.byref(d),
+                                                           ct.c_void_p(stream)),
+                    "acl_fleet_delay_localize_batch")
+            return
         L.check(L.lib().acl_fleet_localize_batch(ct.byref(F), ct.byref(a), ct.c_void_p(stream)),
                 "acl_fleet_localize_batch")
 
@@ -1230,7 +1321,7 @@ class FleetEpisode(_LossyLinks):
                 "ticks": view(self._status, L.FLEET_STATUS_DTYPE)}
 
 
-class FleetEstEpisode(FleetEpisode):
+class FleetEstEpisode(FleetEpisode, _TableLinks):
     """The closed loop on each vehicle's own estimates
     (acl_fleet_est_episode_batch, added within ABI 11): FleetEpisode in which
     no vehicle reads the shared snapshot q. Every track_every control steps
@@ -1248,11 +1339,17 @@ class FleetEstEpisode(FleetEpisode):
     acl_fleet_est_episode_status_t records. The caller may rewrite them
     between runs. diag=True also records, per step, how wrong the tables are
     against the true q (the err2 maxima of the header, m^2).
+    table_latency / max_table_latency / feed_loss as _TableLinks takes them:
+    with any of them the own-estimate steps fly
+    acl_fleet_delay_est_episode_batch (the gossip round takes tables whole
+    rounds late and a vehicle's own feed may drop out; n_missed counts the
+    skipped senses), with none acl_fleet_est_episode_batch as before.
     Raises ValueError on a malformed argument before anything runs."""
 
     def __init__(self, table, fidx, q, vel, Pt=None, params=None, cntrl=None, safety=None,
                  queue_cap=None, max_iter=0, ticks_per_step=10, latency=None, max_latency=None,
-                 loss=None, loss_seed=None, track_every=2, diag=False):
+                 loss=None, loss_seed=None, track_every=2, diag=False, table_latency=None,
+                 max_table_latency=None, feed_loss=None):
         if isinstance(track_every, bool) or not isinstance(track_every, (int, np.integer)) or \
                 track_every < 1:
             raise ValueError(f"FleetEstEpisode: track_every = {track_every!r} must be an int >= 1")
@@ -1264,6 +1361,7 @@ class FleetEstEpisode(FleetEpisode):
                          loss=0 if loss is None else loss, loss_seed=loss_seed)
         self.track_every, self.diag = int(track_every), bool(diag)
         B, n, dev = self.B, self.n, self.device
+        self._table_setup("FleetEstEpisode", table_latency, max_table_latency, feed_loss, B, n, dev)
         self.loc_stamp = torch.zeros((B, n, n), dtype=torch.int32, device=dev)
         self.loc_est = torch.zeros((B, n, n, 3), dtype=torch.float64, device=dev)
         self.loc_round = torch.zeros((B,), dtype=torch.int32, device=dev)
@@ -1304,7 +1402,11 @@ class FleetEstEpisode(FleetEpisode):
                 "P": torch.zeros((steps, B, n), dtype=torch.int16, device=dev),
                 "vflags": torch.zeros((steps, B, n), dtype=torch.int32, device=dev),
             }
-        x = L.FleetEstEpisodeArgs()
+        delayed = own_estimates and self.table_latency is not None
+        y = L.FleetDelayEstEpisodeArgs() if delayed else None
+        x = y.est if delayed else L.FleetEstEpisodeArgs()
+        if delayed:
+            self._table_args("FleetEstEpisode.run", y, "loc_n_missed", "loc_workspace")
         lo = x.lossy
         d = lo.delay
         a = d.base
@@ -1332,9 +1434,14 @@ class FleetEstEpisode(FleetEpisode):
             if hist is not None and self.diag:
                 hist["err2"] = torch.zeros((steps, B, 3), dtype=torch.float64, device=dev)
                 x.err2_hist = hist["err2"].data_ptr()
-            L.check(L.lib().acl_fleet_est_episode_batch(ct.byref(F), ct.byref(x),
-                                                        ct.c_void_p(stream)),
-                    "acl_fleet_est_episode_batch")
+            if delayed:
+                L.check(L.lib().acl_fleet_delay_est_episode_batch(ct.byref(F), ct.byref(y),
+                                                                  ct.c_void_p(stream)),
+                        "acl_fleet_delay_est_episode_batch")
+            else:
+                L.check(L.lib().acl_fleet_est_episode_batch(ct.byref(F), ct.byref(x),
+                                                            ct.c_void_p(stream)),
+                        "acl_fleet_est_episode_batch")
         else:
             L.check(L.lib().acl_fleet_lossy_episode_batch(ct.byref(F), ct.byref(lo),
                                                           ct.c_void_p(stream)),

@@ -878,9 +878,9 @@ acl_status_t acl_fleet_lossy_auction_batch(const acl_formations_t* formations,
  *
  * Not modelled (the auction's START, one control step, the episodes of
  * acl_fleet_est_episode_batch and the trials of acl_fleet_est_trial_batch read
- * the tables, below): gossip latency of whole rounds; outages of a vehicle's
- * own state feed; n > 128; the reference's "make this smarter using
- * Dijkstra's" TODO. */
+ * the tables, below): gossip latency of whole rounds and outages of a
+ * vehicle's own state feed (both are acl_fleet_delay_localize_batch's, below);
+ * n > 128; the reference's "make this smarter using Dijkstra's" TODO. */
 #define ACL_FLEET_LOC_BAD_ROW 0x8 /* localize status.flags: a row is no permutation */
 
 typedef struct {
@@ -908,6 +908,88 @@ typedef struct {
 
 acl_status_t acl_fleet_localize_batch(const acl_formations_t* formations,
                                       const acl_fleet_localize_args_t* args, void* stream);
+
+/* ---- fleet localization on real links: table latency in whole rounds, outages
+ * of a vehicle's own state feed (added within ABI 11) -------------------------
+ * acl_fleet_delay_localize_batch is acl_fleet_localize_batch with two sentences
+ * changed. Everything else holds unchanged: the state arrays, sense / publish /
+ * merge / round += 1, the subscription rule under the receiver's own row of the
+ * moment, "strictly later wins, own stays on ties, lowest sender id among
+ * equals", bad rows, a bad fidx, q_rounds, the status record, and rounds a then
+ * b equals a + b. Added symbols: ACL_ABI_VERSION stays 11.
+ *
+ * Table latency. tlat[b][w][u] is u8, receiver-major; off the diagonal it lies
+ * in 0..max_tlat (a call argument in 0..7), the diagonal is ignored. In round r
+ * receiver w takes from each sender u it subscribes to, at round r under its
+ * own row, the table that u PUBLISHED IN ROUND P = r - tlat[b][w][u]. Every
+ * vehicle's published table of every round is kept by copy in a publication
+ * log in the caller's workspace: max_tlat + 1 slots per swarm, slot
+ * P mod (max_tlat + 1) tagged with its publication round. A table whose slot
+ * does not carry tag P does not exist: P < 0, a table published before the
+ * swarm came to this entry, a zero-filled workspace. Such a table is not
+ * delivered and is not counted as lost. An existing table is LOST iff
+ *     loss[b][w][u] == 0xFFFF ||
+ *     (link_hash(seed[b], w, u, P, 0xFFFFFFFF) >> 16) < loss[b][w][u]
+ * the rule above with the publication round as the publication word; at
+ * latency 0 it is the same hash. The tlat, loss and seed of the call in whose
+ * round a table is due decide that table; all three may differ from call to
+ * call (the merge is monotone in the stamp, so a table that is taken twice, or
+ * never, harms nothing). max_tlat is fixed for the life of a workspace, like n
+ * and B. A swarm with an off-diagonal entry above max_tlat gets
+ * ACL_FLEET_BAD_INPUT and is untouched in every respect, exactly like a bad
+ * fidx: stamp, est, round, n_lost, n_missed and its log.
+ *
+ * Feed outage. feed_loss[b][w] is u16; NULL: never. In round r vehicle w's
+ * sense is skipped iff
+ *     feed_loss[b][w] == 0xFFFF ||
+ *     (link_hash(seed[b], w, w, r, 0xFFFFFFFE) >> 16) < feed_loss[b][w]
+ * The word (w << 16) | w names no link, and no bid or table has iter
+ * 0xFFFFFFFE: an outage is independent of every bid's and table's fate under
+ * the same seed. A skipped sense leaves stamp[w][w] and est[w][w] as they
+ * stand; the vehicle publishes and merges as usual, its own entry included, as
+ * updateVehicle does. A skipped sense counts once in n_missed[b][w] (i32,
+ * in/out). feed_loss requires seed and n_missed (seed may then stand without
+ * loss).
+ *
+ * Workspace: acl_fleet_delay_localize_workspace_bytes(n, B, max_tlat) bytes (0
+ * for arguments out of range), zero-filled once by the caller. Per swarm, with
+ * M = max_tlat + 1: 8 i32 slot tags (publication round + 1; 0: empty), M slots
+ * of n^2 positions (3 f64 each), M slots of n^2 stamps (i32), padded to a
+ * multiple of 8: 32 + 28 M n^2 bytes, 0.46 MB per slot and swarm at n = 128.
+ *
+ * Reductions:
+ *  1. With tlat all zero and feed_loss NULL this is acl_fleet_localize_batch
+ *     bit for bit, whatever the workspace holds: stamp, est, round, n_lost and
+ *     status, with and without loss.
+ *  2. Rounds a then b equals a + b, with tables in flight across the boundary.
+ *  3. On a connected graph with identity rows, no loss and every link at d
+ *     rounds, a vehicle k hops away is known after k (d + 1) rounds and is
+ *     k (d + 1) - 1 rounds old from then on.
+ *
+ * Argument errors, reported before any HIP call: those of
+ * acl_fleet_localize_batch (seed without loss is allowed with feed_loss);
+ * max_tlat outside 0..7; feed_loss without seed or without n_missed; with
+ * B > 0: tlat NULL, workspace NULL or workspace_bytes too small.
+ * Stream-ordered, never synchronises.
+ *
+ * Not modelled: latencies finer than a round; outages that depend on history
+ * (bursts); n > 128. The closed loop on this entry is
+ * acl_fleet_delay_est_episode_batch; the trials on own estimates still run
+ * acl_fleet_localize_batch. */
+typedef struct {
+  acl_fleet_localize_args_t base;
+  const uint8_t* tlat;       /* [B][n][n] receiver-major, rounds; diagonal ignored */
+  int32_t max_tlat;          /* 0..7 */
+  const uint16_t* feed_loss; /* [B][n] or NULL */
+  int32_t* n_missed;         /* [B][n] in/out; required with feed_loss */
+  void* workspace;           /* acl_fleet_delay_localize_workspace_bytes, zero-filled once */
+  size_t workspace_bytes;
+} acl_fleet_delay_localize_args_t;
+
+size_t acl_fleet_delay_localize_workspace_bytes(int32_t n, int32_t B, int32_t max_tlat);
+acl_status_t acl_fleet_delay_localize_batch(const acl_formations_t* formations,
+                                            const acl_fleet_delay_localize_args_t* args,
+                                            void* stream);
 
 /* ---- the fleet auction started from each vehicle's own estimates (added
  * within ABI 11) -------------------------------------------------------------
@@ -1448,7 +1530,8 @@ acl_status_t acl_fleet_lossy_episode_batch(const acl_formations_t* formations,
  * step for step, the control step's sum order apart.
  * Not modelled: a loss matrix of its own for tables (the trials on own
  * estimates are acl_fleet_est_trial_batch, below); gossip latency of whole
- * rounds; outages of a vehicle's own state feed; n > 128. */
+ * rounds and outages of a vehicle's own state feed (both are
+ * acl_fleet_delay_est_episode_batch's, below); n > 128. */
 typedef struct {
   int32_t rounds_run;   /* gossip rounds, accumulated */
   int32_t n_unknown;    /* entries with stamp 0 after the last round run */
@@ -1476,6 +1559,42 @@ size_t acl_fleet_est_episode_workspace_bytes(int32_t n, int32_t B, int32_t queue
 acl_status_t acl_fleet_est_episode_batch(const acl_formations_t* formations,
                                          const acl_fleet_est_episode_args_t* args,
                                          void* stream);
+
+/* ---- the episodes on own estimates with tables on real links (added within
+ * ABI 11) ---------------------------------------------------------------------
+ * acl_fleet_delay_est_episode_batch is acl_fleet_est_episode_batch with one
+ * call replaced: the gossip round of step 0 is one round of
+ * acl_fleet_delay_localize_batch under tlat, max_tlat and feed_loss, with the
+ * same link.loss / link.seed, on the fidx of the hand-off (a swarm the hand-off
+ * skips is untouched by the round as well, its log and loc_n_missed included).
+ * Skipped senses count in loc_n_missed. A swarm whose tlat holds an entry above
+ * max_tlat flies on with its trackers standing still. The localization
+ * workspace (acl_fleet_delay_localize_workspace_bytes(n, B, max_tlat),
+ * zero-filled once) is its own; the episode workspace is that of
+ * acl_fleet_est_episode_batch and its layout does not move, so an episode may
+ * move between the two entries from call to call.
+ * With tlat all zero and feed_loss NULL this is acl_fleet_est_episode_batch
+ * step for step, byte for byte.
+ * Argument errors, reported before any HIP call: those of
+ * acl_fleet_est_episode_batch on `est`; max_tlat outside 0..7; feed_loss
+ * without loc_n_missed; with B > 0 and steps > 0: tlat NULL, loc_workspace NULL
+ * or loc_workspace_bytes too small.
+ * Not modelled: what acl_fleet_delay_localize_batch and
+ * acl_fleet_est_episode_batch do not model; the trials on own estimates
+ * (acl_fleet_est_trial_batch) still gossip within the round. */
+typedef struct {
+  acl_fleet_est_episode_args_t est;
+  const uint8_t* tlat;       /* [B][n][n] receiver-major, rounds; diagonal ignored */
+  int32_t max_tlat;          /* 0..7 */
+  const uint16_t* feed_loss; /* [B][n] or NULL */
+  int32_t* loc_n_missed;     /* [B][n] in/out; required with feed_loss */
+  void* loc_workspace;       /* acl_fleet_delay_localize_workspace_bytes, zero-filled once */
+  size_t loc_workspace_bytes;
+} acl_fleet_delay_est_episode_args_t;
+
+acl_status_t acl_fleet_delay_est_episode_batch(const acl_formations_t* formations,
+                                               const acl_fleet_delay_est_episode_args_t* args,
+                                               void* stream);
 
 /* ---- batched Monte-Carlo trials (ABI 9; SURVEY §8f widening of row f1) ---
  * B independent trials of aclswarm_sim's supervisor (aclswarm_sim/nodes/

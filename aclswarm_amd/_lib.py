@@ -51,6 +51,7 @@ EXPORTS = (
     "acl_fleet_est_episode_workspace_bytes", "acl_fleet_est_episode_batch",
     "acl_fleet_est_trial_workspace_bytes", "acl_fleet_est_trial_init",
     "acl_fleet_est_trial_batch",
+    "acl_fleet_delay_est_trial_init", "acl_fleet_delay_est_trial_batch",
     "acl_default_episode_params", "acl_episode_workspace_bytes", "acl_episode_batch",
     "acl_default_trial_params", "acl_trial_workspace_bytes", "acl_trial_init", "acl_trial_batch",
     "acl_fleet_trial_workspace_bytes", "acl_fleet_trial_init", "acl_fleet_trial_batch",
@@ -374,6 +375,24 @@ class FleetEstTrialArgs(ct.Structure):
                                    "xst", "err2_hist")]
 
 
+class FleetDelayEstTrialArgs(ct.Structure):
+    """acl_fleet_delay_est_trial_args_t (added within ABI 11): the trials on own
+    estimates with tables on real links, and the encounter record."""
+    _fields_ = [("est", FleetEstTrialArgs), ("tlat", ct.c_void_p), ("max_tlat", ct.c_int32),
+                ("feed_loss", ct.c_void_p), ("loc_n_missed", ct.c_void_p),
+                ("loc_workspace", ct.c_void_p), ("loc_workspace_bytes", ct.c_size_t)] + [
+        (n, ct.c_void_p) for n in ("enc", "enc_blind", "enc_ghost", "enc_hist")]
+
+
+# acl_fleet_encounter_status_t (32 bytes) and acl_fleet_encounter_step_t (24 bytes)
+FLEET_ENCOUNTER_STATUS_DTYPE = np.dtype(
+    [("sep2_min", "<f8"), ("step", "<i4"), ("i", "<u2"), ("j", "<u2"), ("n_breach", "<i4"),
+     ("n_blind", "<i4"), ("n_ghost", "<i4"), ("reserved", "<i4")])
+FLEET_ENCOUNTER_STEP_DTYPE = np.dtype(
+    [("sep2", "<f8"), ("i", "<u2"), ("j", "<u2"), ("n_breach", "<u2"), ("n_blind", "<u2"),
+     ("n_ghost", "<u2"), ("pad", "<u2", (3,))])
+
+
 class GemmJobRec(ct.Structure):
     """acl_internal_gemm_job_t (csrc/admm.hip, a test hook's record): GemmJob
     (csrc/gemm_f64.h) field for field; pointers are device addresses."""
@@ -529,6 +548,11 @@ def lib():
     L.acl_fleet_est_trial_batch.argtypes = [ct.POINTER(Formations),
                                             ct.POINTER(FleetEstTrialArgs), VP]
     L.acl_fleet_est_trial_batch.restype = ct.c_int
+    L.acl_fleet_delay_est_trial_init.argtypes = [ct.POINTER(FleetDelayEstTrialArgs), I32, VP]
+    L.acl_fleet_delay_est_trial_init.restype = ct.c_int
+    L.acl_fleet_delay_est_trial_batch.argtypes = [ct.POINTER(Formations),
+                                                  ct.POINTER(FleetDelayEstTrialArgs), VP]
+    L.acl_fleet_delay_est_trial_batch.restype = ct.c_int
     L.acl_write_assignment_log.argtypes = [ct.c_char_p, I32, VP, VP, VP, VP, VP, VP]
     L.acl_write_assignment_log.restype = ct.c_int
     L.acl_read_assignment_log.argtypes = [ct.c_char_p, ct.POINTER(I32), VP, VP, VP, VP, VP, VP]

@@ -32,6 +32,7 @@
 #include "../../include/aclswarm_amd.h"
 #include "common.h"
 #include "control_dev.h"     // gain_segments, saturate, gate_decide, pair_e, pair_s2
+#include "ca_candidate_dev.h"  // ca_thr2hi, ca_candidate
 #include "ca_resolve_dev.h"  // ca_resolve_wave / _general / _serial
 #include "fleet_dev.h"       // kFleetMaxN
 #include "own_row_dev.h"     // own_row_check
@@ -375,8 +376,7 @@ __global__ void __launch_bounds__(kEcBlock) fleet_est_control_kernel(const EstCt
   const EstCtlArgs P2 = est_ctl_args();
   const acl_safety_params_t sp = {P2->s.max_vel_xy, P2->s.max_vel_z, P2->s.d_avoid_thresh,
                                   P2->s.r_keep_out};
-  const double thr_hi = sp.d_avoid_thresh * (1.0 + 0x1p-40);
-  const double thr2hi = thr_hi * thr_hi;
+  const double thr2hi = ca_thr2hi(sp.d_avoid_thresh);
   int mine = 0;  // commands this wave modified (lane 0)
   for (int v = wave; v < n; v += kEcWaves) {
     // the lane id afresh for every vehicle: the sorting networks' lane
@@ -399,13 +399,9 @@ __global__ void __launch_bounds__(kEcBlock) fleet_est_control_kernel(const EstCt
         if (j < n && j != v) {
           dx = T[3 * j] - qv0;
           dy = T[3 * j + 1] - qv1;
+          // (ca_candidate_dev.h: the sqrt is taken only near the threshold)
           const double s2 = dx * dx + dy * dy;
-          // |dq_xy|^2 above (thr (1 + 2^-40))^2 is far for certain: the sqrt
-          // is taken only near the threshold (NaN included)
-          if (!(s2 > thr2hi)) {
-            dd = sqrt(s2);
-            cand = !(dd > sp.d_avoid_thresh);
-          }
+          ca_candidate(s2, thr2hi, sp.d_avoid_thresh, cand, dd);
         }
         const unsigned long long m = __ballot(cand);
         if (cand) {

@@ -66,7 +66,23 @@
 //                                are against the true q, err2_nbr over the
 //                                running controllers only
 //
+//
+// acl_fleet_delay_est_trial_init / acl_fleet_delay_est_trial_batch are those
+// trials with the gossip round acl_fleet_delay_localize_batch's (table latency
+// in whole rounds, feed outages; the publication log lives in the caller's
+// loc_workspace) and, when asked for, the encounter record. Three more kernels,
+// at the end of the file as well:
+//   fleet_trial_tlat_handoff_kernel  the call's first hand-off with the table
+//                                    latencies in the input check
+//   fleet_trial_enc_init_kernel      the empty encounter record
+//   fleet_trial_encounter_kernel     after the post kernel: true separation,
+//                                    breaches, and the candidates of
+//                                    collisionAvoidance on the true q against
+//                                    those on each vehicle's table (blind,
+//                                    ghost), by ca_candidate_dev.h's test
+//
 // Compiled with -ffp-contract=off (trial_dev.h).
+#include "ca_candidate_dev.h"
 #include "common.h"
 #include "fleet_loop_dev.h"
 #include "trial_dev.h"
@@ -418,6 +434,16 @@ constexpr FtrDelay kNoDelay = {nullptr, 0, 0, nullptr};
 acl_status_t ftr_est_init_launch(const acl_amd::FtrOwn& O, int n, int B, hipStream_t s);
 acl_status_t ftr_est_post_launch(const acl_amd::FtrPost& X, bool diag, hipStream_t s);
 
+// acl_fleet_delay_est_trial_batch's additions to the own-estimate loop (NULL:
+// the other entries) and its three kernels (at the end of the file). The block
+// travels beside FtrOwn, not in it: FtrOwn is the init kernel's argument.
+using FtrTables = acl_fleet_delay_est_trial_args_t;
+acl_status_t ftr_tlat_handoff_launch(const acl_amd::FtrArgs& A, const FtrTables& T,
+                                     hipStream_t s);
+acl_status_t ftr_enc_init_launch(const FtrTables& T, int n, int B, hipStream_t s);
+acl_status_t ftr_encounter_launch(const acl_amd::FtrPost& X, const FtrTables& T, int step,
+                                  const acl_safety_params_t& sp, hipStream_t s);
+
 // (after ftr_check; before anything else reads max_lat)
 acl_status_t ftr_delay(const acl_fleet_delay_trial_args_t* d, const char* who, FtrDelay* out) {
   if (d->max_lat < 1 || d->max_lat > acl_amd::kFleetMaxLat)
@@ -449,7 +475,8 @@ acl_status_t ftr_check(const acl_fleet_trial_args_t* a, int n, const char* who) 
 }
 
 acl_status_t ftr_pointers(const acl_fleet_trial_args_t* a, int n, const char* who,
-                          const FtrDelay& dl, const acl_amd::FtrOwn* own = nullptr) {
+                          const FtrDelay& dl, const acl_amd::FtrOwn* own = nullptr,
+                          const FtrTables* tb = nullptr) {
   auto fail = [&](const char* what) { return acl_amd::fleet_error(who, what); };
   if (!a->fseq || !a->fidx || !a->q || !a->vel || !a->P || !a->ts || !a->ctl_on || !a->ring_u ||
       !a->ring_ca || !a->posf || !a->dist || !a->t_conv || !a->t_avoid || !a->n_assign ||
@@ -465,6 +492,11 @@ acl_status_t ftr_pointers(const acl_fleet_trial_args_t* a, int n, const char* wh
   if (own && (!own->loc_stamp || !own->loc_est || !own->loc_round || !own->loc_n_lost ||
               !own->loc_Pt || !own->xst))
     return fail("loc_stamp, loc_est, loc_round, loc_n_lost, loc_Pt or xst is NULL");
+  if (tb && !tb->tlat) return fail("tlat is NULL");
+  if (tb && !tb->loc_workspace) return fail("loc_workspace is NULL");
+  if (tb && tb->loc_workspace_bytes <
+                acl_fleet_delay_localize_workspace_bytes(n, a->B, tb->max_tlat))
+    return fail("loc_workspace_bytes is too small (acl_fleet_delay_localize_workspace_bytes)");
   if (a->workspace_bytes < acl_amd::ftr_layout(n, a->B, a->queue_cap, dl.R, own != nullptr).total)
     return fail(own    ? "workspace_bytes is too small (acl_fleet_est_trial_workspace_bytes)"
                 : dl.R ? "workspace_bytes is too small (acl_fleet_delay_trial_workspace_bytes)"
@@ -529,10 +561,11 @@ acl_amd::FtrArgs ftr_args(const acl_fleet_trial_args_t* a, int n, const acl_amd:
 // (acl_fleet_est_trial_init): the workspace with its tail, and the
 // own-estimate entry's arrays.
 acl_status_t ftr_init(const char* who, const acl_fleet_trial_args_t* a, int n, const FtrDelay& dl,
-                      void* stream, const acl_amd::FtrOwn* own = nullptr) {
+                      void* stream, const acl_amd::FtrOwn* own = nullptr,
+                      const FtrTables* tb = nullptr) {
   using namespace acl_amd;
   if (a->B == 0) return ACL_OK;
-  const acl_status_t r = ftr_pointers(a, n, who, dl, own);
+  acl_status_t r = ftr_pointers(a, n, who, dl, own, tb);
   if (r != ACL_OK) return r;
   const TrialDev D = ftr_trial_dev(a, n, dl);
   const FtrArgs A = ftr_args(a, n, D, dl);
@@ -549,7 +582,16 @@ acl_status_t ftr_init(const char* who, const acl_fleet_trial_args_t* a, int n, c
   hipLaunchKernelGGL(fleet_trial_init_kernel, dim3(a->B), dim3(kFleetLoopBlock), 0, s, D, A, I);
   if (hipGetLastError() != hipSuccess)
     return acl__set_error("fleet_trial_init_kernel launch failed");
-  return own ? ftr_est_init_launch(*own, n, a->B, s) : ACL_OK;
+  if (!own) return ACL_OK;
+  r = ftr_est_init_launch(*own, n, a->B, s);
+  if (r != ACL_OK || !tb) return r;
+  // an empty publication log, no sense missed, an empty encounter record
+  const size_t log_bytes = acl_fleet_delay_localize_workspace_bytes(n, a->B, tb->max_tlat);
+  if (hipMemsetAsync(tb->loc_workspace, 0, log_bytes, s) != hipSuccess ||
+      (tb->loc_n_missed &&
+       hipMemsetAsync(tb->loc_n_missed, 0, (size_t)a->B * n * sizeof(int32_t), s) != hipSuccess))
+    return acl__set_error("hipMemsetAsync failed");
+  return tb->enc ? ftr_enc_init_launch(*tb, n, a->B, s) : ACL_OK;
 }
 
 // The host loop of acl_fleet_trial_batch, acl_fleet_delay_trial_batch and
@@ -559,14 +601,18 @@ acl_status_t ftr_init(const char* who, const acl_fleet_trial_args_t* a, int n, c
 // own (with dl.link): the trial on own estimates -- after the pre kernel a
 // gossip round every track_every steps under loc_Pt, the ticks
 // acl_fleet_est_auction_batch's, the post kernel, the control step
-// acl_fleet_est_control_batch's.
+// acl_fleet_est_control_batch's. tb (with own): the round is
+// acl_fleet_delay_localize_batch's under tb's table links, the first hand-off
+// checks the table latencies too, and with tb->enc the encounter kernel follows
+// the post kernel. Without tb nothing below differs from what it was.
 acl_status_t ftr_run(const char* who, const acl_formations_t* F, const acl_fleet_trial_args_t* a,
-                     const FtrDelay& dl, void* stream, const acl_amd::FtrOwn* own = nullptr) {
+                     const FtrDelay& dl, void* stream, const acl_amd::FtrOwn* own = nullptr,
+                     const FtrTables* tb = nullptr) {
   using namespace acl_amd;
   const int n = F->n;
   const int B = a->B;
   if (B == 0 || a->steps == 0) return ACL_OK;
-  acl_status_t r = ftr_pointers(a, n, who, dl, own);
+  acl_status_t r = ftr_pointers(a, n, who, dl, own, tb);
   if (r != ACL_OK) return r;
   if (F->n_formations < 1) return fleet_error(who, "n_formations < 1");
   const bool delay = dl.R != 0;
@@ -597,7 +643,8 @@ acl_status_t ftr_run(const char* who, const acl_formations_t* F, const acl_fleet
   // the trial on own estimates: the three public entries' arguments. The
   // gossip subscribes under loc_Pt and sees the formation of this step (-1 for
   // a finished trial, as the ticks and the control step do).
-  acl_fleet_localize_args_t lo = {};
+  acl_fleet_delay_localize_args_t dlo = {};
+  acl_fleet_localize_args_t& lo = dlo.base;
   acl_fleet_est_control_args_t ec = {};
   FtrPost X = {};
   if (own) {
@@ -615,10 +662,18 @@ acl_status_t ftr_run(const char* who, const acl_formations_t* F, const acl_fleet
     X.ctl_on = a->ctl_on; X.adj = F->adj; X.q = a->q; X.est = own->loc_est;
     X.stamp = own->loc_stamp; X.Pt = a->Pt; X.loc_Pt = own->loc_Pt; X.lst = lst;
     X.xst = own->xst; X.err2_hist = own->err2_hist;
+    if (tb) {
+      dlo.tlat = tb->tlat; dlo.max_tlat = tb->max_tlat; dlo.feed_loss = tb->feed_loss;
+      dlo.n_missed = tb->loc_n_missed; dlo.workspace = tb->loc_workspace;
+      dlo.workspace_bytes = tb->loc_workspace_bytes;
+    }
   }
 
   // the call's input check and its hand-off from the rows alone
-  if (delay)
+  if (tb) {
+    r = ftr_tlat_handoff_launch(A, *tb, s);
+    if (r != ACL_OK) return r;
+  } else if (delay)
     hipLaunchKernelGGL((fleet_trial_handoff_kernel<true, true>), dim3(B), dim3(kFleetLoopBlock), 0,
                        s, A);
   else
@@ -637,7 +692,8 @@ acl_status_t ftr_run(const char* who, const acl_formations_t* F, const acl_fleet
       return acl__set_error("fleet_trial_pre_kernel launch failed");
     if (own && D.step % own->track_every == 0) {
       // after this step's commit; the round senses q as it stands at the start of the step
-      r = acl_fleet_localize_batch(F, &lo, stream);
+      r = tb ? acl_fleet_delay_localize_batch(F, &dlo, stream)
+             : acl_fleet_localize_batch(F, &lo, stream);
       if (r != ACL_OK) return r;
       X.round = 1;
     } else {
@@ -649,6 +705,11 @@ acl_status_t ftr_run(const char* who, const acl_formations_t* F, const acl_fleet
       X.k = k;
       r = ftr_est_post_launch(X, own->diag != 0, s);
       if (r != ACL_OK) return r;
+      if (tb && tb->enc) {
+        // q and the tables as this step's control step will read them
+        r = ftr_encounter_launch(X, *tb, D.step, a->safety, s);
+        if (r != ACL_OK) return r;
+      }
     }
     hipLaunchKernelGGL(fleet_trial_handoff_kernel<false>, dim3(B), dim3(kFleetLoopBlock), 0, s, A);
     if (hipGetLastError() != hipSuccess)
@@ -951,4 +1012,281 @@ extern "C" acl_status_t acl_fleet_est_trial_batch(const acl_formations_t* F,
   acl_amd::FtrOwn own;
   const acl_status_t r = ftr_est_check(x, F->n, who, &dl, &own);
   return r != ACL_OK ? r : ftr_run(who, F, &x->lossy.delay.base, dl, stream, &own);
+}
+
+// ---- the trials on own estimates with tables on real links, and the encounter
+// record -------------------------------------------------------------------------
+// (Templates below everything else, like the kernels above: the existing
+// kernels are emitted as before.)
+namespace acl_amd {
+
+// what the encounter kernels read and write beside FtrPost
+struct FtrEnc {
+  int step;                             // the global step (enc[b].step)
+  double d_avoid_thresh, r_keep_out;    // Safety's
+  acl_fleet_encounter_status_t* enc;    // [B]
+  int32_t* blind;                       // [B][n]
+  int32_t* ghost;                       // [B][n]
+  acl_fleet_encounter_step_t* hist;     // [steps][B] or NULL
+};
+
+// The call's first hand-off (fleet_trial_handoff_kernel<true, true>) with the
+// swarm's table latencies in the input check: an off-diagonal entry above
+// max_tlat makes the swarm BAD_INPUT for the call before anything is written.
+template <class Args>
+__global__ void __launch_bounds__(kFleetLoopBlock) fleet_trial_tlat_handoff_kernel(
+    const Args A, const uint8_t* tlat, const int max_tlat) {
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x, n = A.n;
+  bool bad = false, differs = false;
+  const uint8_t* tb = tlat + (size_t)b * n * n;
+  for (int k = tid; k < n * n; k += kFleetLoopBlock) {
+    const int w = k / n;
+    if (k - w * n != w && (int)tb[k] > max_tlat) bad = true;
+  }
+  bad = fleet_input_check<true>(A, b, bad, differs);
+  fleet_input_mark(A, b, bad);
+  if (bad) return;  // block-uniform
+  const bool mixed = fleet_handoff_write(A, b, differs);
+  if (tid == 0) A.ts[b].per_vehicle = mixed ? 1 : 0;
+}
+
+template <class Enc>
+__global__ void __launch_bounds__(kFleetLoopBlock) fleet_trial_enc_init_kernel(const Enc E,
+                                                                                 const int n) {
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
+  for (int v = tid; v < n; v += kFleetLoopBlock) {
+    E.blind[(size_t)b * n + v] = 0;
+    E.ghost[(size_t)b * n + v] = 0;
+  }
+  if (tid == 0) {
+    acl_fleet_encounter_status_t e = {};
+    e.sep2_min = __longlong_as_double(0x7FF0000000000000ll);
+    e.step = -1;
+    e.i = e.j = 0xFFFFu;
+    E.enc[b] = e;
+  }
+}
+
+// (s2, key) < (t2, tkey): the smaller separation, among equals the lower pair
+// key (i << 16 | j). A NaN is never held, so this is a total order.
+__device__ __forceinline__ bool ftr_sep_less(double s2, unsigned key, double t2, unsigned tkey) {
+  return s2 < t2 || (s2 == t2 && key < tkey);
+}
+
+// After the post kernel, before the hand-off takes the step's flags: one
+// workgroup per swarm, a wave per vehicle (v = wave, wave + 4, ...), lane l owns
+// j = l and l + 64; the plane of q[b] in LDS. Per vehicle v the wave
+//   - takes s2 = |q_j - q_v|_xy^2 for every j != v (dx * dx + dy * dy; bitwise
+//     symmetric in v and j), and over j > v the minimum with its pair and the
+//     count below r_keep_out^2: every unordered pair once;
+//   - if v's controller runs this step (the post kernel's `on`), applies
+//     ca_candidate to s2 and to |est[v][j] - est[v][v]|_xy^2, the expression
+//     the control kernel forms, and counts blind and ghost by ballot.
+// The counts live in wave-uniform registers; the minimum is reduced by an xor
+// butterfly under a total order, so the result does not depend on which wave or
+// lane saw a pair. No atomics, no scratch. A BAD_INPUT swarm and a finished
+// trial return before anything is read.
+template <class Enc>
+__global__ void __launch_bounds__(kFleetLoopBlock) fleet_trial_encounter_kernel(const FtrPost A,
+                                                                                 const Enc E) {
+  __shared__ double q_s[2 * kFleetMaxN];
+  __shared__ double sep_s[kFleetLoopBlock / 64];
+  __shared__ unsigned key_s[kFleetLoopBlock / 64];
+  __shared__ int cnt_s[kFleetLoopBlock / 64][3];
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x, n = A.n;
+  if (A.skip[b] != 0 || A.fidx_eff[b] < 0) return;  // block-uniform
+  const int lane = tid & 63, wv = tid >> 6;
+  const size_t vb = (size_t)b * n;
+  {
+    const double* gq = A.q + vb * 3;
+    for (int j = tid; j < n; j += kFleetLoopBlock) {
+      q_s[2 * j] = gq[3 * j];
+      q_s[2 * j + 1] = gq[3 * j + 1];
+    }
+  }
+  __syncthreads();
+  const double thr = E.d_avoid_thresh;
+  const double thr2hi = ca_thr2hi(thr);
+  const double keep2 = E.r_keep_out * E.r_keep_out;
+  double best = __longlong_as_double(0x7FF0000000000000ll);  // +inf
+  unsigned bkey = 0xFFFFFFFFu;
+  int n_breach = 0, n_blind = 0, n_ghost = 0;  // wave-uniform
+  for (int v = wv; v < n; v += kFleetLoopBlock / 64) {
+    const double qv0 = q_s[2 * v], qv1 = q_s[2 * v + 1];
+    const bool on = A.ctl_on[vb + v] != 0 || (A.vf[vb + v] & ACL_FLEET_V_ADOPTED) != 0;
+    const double* T = A.est + (vb + v) * (size_t)n * 3;
+    double tv0 = 0.0, tv1 = 0.0;
+    if (on) {  // wave-uniform
+      tv0 = T[3 * v];
+      tv1 = T[3 * v + 1];
+    }
+    int vb_blind = 0, vb_ghost = 0;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int j = lane + 64 * s;
+      bool breach = false, blind = false, ghost = false;
+      if (j < n && j != v) {
+        const double dx = q_s[2 * j] - qv0;
+        const double dy = q_s[2 * j + 1] - qv1;
+        const double s2 = dx * dx + dy * dy;
+        if (j > v) {
+          const unsigned key = ((unsigned)v << 16) | (unsigned)j;
+          if (ftr_sep_less(s2, key, best, bkey)) {
+            best = s2;
+            bkey = key;
+          }
+          breach = s2 < keep2;
+        }
+        if (on) {
+          double dd = 0.0;
+          bool ct = false, ce = false;
+          ca_candidate(s2, thr2hi, thr, ct, dd);
+          const double ex = T[3 * j] - tv0;
+          const double ey = T[3 * j + 1] - tv1;
+          ca_candidate(ex * ex + ey * ey, thr2hi, thr, ce, dd);
+          blind = ct && !ce;
+          ghost = !ct && ce;
+        }
+      }
+      n_breach += __popcll(__ballot(breach));
+      vb_blind += __popcll(__ballot(blind));
+      vb_ghost += __popcll(__ballot(ghost));
+    }
+    if (lane == 0 && on) {
+      E.blind[vb + v] += vb_blind;
+      E.ghost[vb + v] += vb_ghost;
+    }
+    n_blind += vb_blind;
+    n_ghost += vb_ghost;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int lo = __shfl_xor(__double2loint(best), o, 64);
+    const int hi = __shfl_xor(__double2hiint(best), o, 64);
+    const unsigned k2 = (unsigned)__shfl_xor((int)bkey, o, 64);
+    const double y = __hiloint2double(hi, lo);
+    if (ftr_sep_less(y, k2, best, bkey)) {
+      best = y;
+      bkey = k2;
+    }
+  }
+  if (lane == 0) {
+    sep_s[wv] = best;
+    key_s[wv] = bkey;
+    cnt_s[wv][0] = n_breach;
+    cnt_s[wv][1] = n_blind;
+    cnt_s[wv][2] = n_ghost;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int c0 = cnt_s[0][0], c1 = cnt_s[0][1], c2 = cnt_s[0][2];
+    for (int w = 1; w < kFleetLoopBlock / 64; ++w) {
+      if (ftr_sep_less(sep_s[w], key_s[w], best, bkey)) {
+        best = sep_s[w];
+        bkey = key_s[w];
+      }
+      c0 += cnt_s[w][0];
+      c1 += cnt_s[w][1];
+      c2 += cnt_s[w][2];
+    }
+    const uint16_t pi = (uint16_t)(bkey >> 16), pj = (uint16_t)(bkey & 0xFFFFu);
+    if (E.hist) {
+      acl_fleet_encounter_step_t h = {};
+      h.sep2 = best;
+      h.i = pi; h.j = pj;
+      h.n_breach = (uint16_t)c0; h.n_blind = (uint16_t)c1; h.n_ghost = (uint16_t)c2;
+      E.hist[(size_t)A.k * A.B + b] = h;
+    }
+    acl_fleet_encounter_status_t e = E.enc[b];
+    if (best < e.sep2_min) {  // strictly: the earliest step keeps the record
+      e.sep2_min = best;
+      e.step = E.step;
+      e.i = pi; e.j = pj;
+    }
+    e.n_breach += c0;
+    e.n_blind += c1;
+    e.n_ghost += c2;
+    E.enc[b] = e;
+  }
+}
+
+}  // namespace acl_amd
+
+namespace {
+
+acl_status_t ftr_tlat_handoff_launch(const acl_amd::FtrArgs& A, const FtrTables& T,
+                                     hipStream_t s) {
+  using namespace acl_amd;
+  hipLaunchKernelGGL(fleet_trial_tlat_handoff_kernel<FtrArgs>, dim3(A.B), dim3(kFleetLoopBlock), 0,
+                     s, A, T.tlat, (int)T.max_tlat);
+  if (hipGetLastError() != hipSuccess)
+    return acl__set_error("fleet_trial_tlat_handoff_kernel launch failed");
+  return ACL_OK;
+}
+
+acl_amd::FtrEnc ftr_enc(const FtrTables& T, int step, const acl_safety_params_t& sp) {
+  acl_amd::FtrEnc E = {};
+  E.step = step; E.d_avoid_thresh = sp.d_avoid_thresh; E.r_keep_out = sp.r_keep_out;
+  E.enc = T.enc; E.blind = T.enc_blind; E.ghost = T.enc_ghost; E.hist = T.enc_hist;
+  return E;
+}
+
+acl_status_t ftr_enc_init_launch(const FtrTables& T, int n, int B, hipStream_t s) {
+  using namespace acl_amd;
+  const FtrEnc E = ftr_enc(T, 0, acl_safety_params_t{});
+  hipLaunchKernelGGL(fleet_trial_enc_init_kernel<FtrEnc>, dim3(B), dim3(kFleetLoopBlock), 0, s, E,
+                     n);
+  if (hipGetLastError() != hipSuccess)
+    return acl__set_error("fleet_trial_enc_init_kernel launch failed");
+  return ACL_OK;
+}
+
+acl_status_t ftr_encounter_launch(const acl_amd::FtrPost& X, const FtrTables& T, int step,
+                                  const acl_safety_params_t& sp, hipStream_t s) {
+  using namespace acl_amd;
+  const FtrEnc E = ftr_enc(T, step, sp);
+  hipLaunchKernelGGL(fleet_trial_encounter_kernel<FtrEnc>, dim3(X.B), dim3(kFleetLoopBlock), 0, s,
+                     X, E);
+  if (hipGetLastError() != hipSuccess)
+    return acl__set_error("fleet_trial_encounter_kernel launch failed");
+  return ACL_OK;
+}
+
+// the argument errors of the two entries that need no pointer into the batch
+acl_status_t ftr_tables_check(const acl_fleet_delay_est_trial_args_t* y, int n, const char* who,
+                              FtrDelay* dl, acl_amd::FtrOwn* own) {
+  const acl_status_t r = ftr_est_check(&y->est, n, who, dl, own);
+  if (r != ACL_OK) return r;
+  if (y->max_tlat < 0 || y->max_tlat > 7)
+    return acl_amd::fleet_error(who, "max_tlat out of range [0, 7]");
+  if (y->feed_loss && !y->loc_n_missed)
+    return acl_amd::fleet_error(who, "feed_loss is given and loc_n_missed is NULL");
+  if (y->enc && (!y->enc_blind || !y->enc_ghost))
+    return acl_amd::fleet_error(who, "enc is given and enc_blind or enc_ghost is NULL");
+  return ACL_OK;
+}
+
+}  // namespace
+
+extern "C" acl_status_t acl_fleet_delay_est_trial_init(const acl_fleet_delay_est_trial_args_t* y,
+                                                       int32_t n, void* stream) {
+  static const char who[] = "acl_fleet_delay_est_trial_init";
+  if (!y) return acl__set_error("acl_fleet_delay_est_trial_init: null argument");
+  FtrDelay dl;
+  acl_amd::FtrOwn own;
+  const acl_status_t r = ftr_tables_check(y, n, who, &dl, &own);
+  if (r != ACL_OK) return r;
+  dl.link = nullptr;  // (as acl_fleet_est_trial_init)
+  return ftr_init(who, &y->est.lossy.delay.base, n, dl, stream, &own, y);
+}
+
+extern "C" acl_status_t acl_fleet_delay_est_trial_batch(const acl_formations_t* F,
+                                                        const acl_fleet_delay_est_trial_args_t* y,
+                                                        void* stream) {
+  static const char who[] = "acl_fleet_delay_est_trial_batch";
+  if (!F || !y) return acl__set_error("acl_fleet_delay_est_trial_batch: null argument");
+  FtrDelay dl;
+  acl_amd::FtrOwn own;
+  const acl_status_t r = ftr_tables_check(y, F->n, who, &dl, &own);
+  return r != ACL_OK ? r : ftr_run(who, F, &y->est.lossy.delay.base, dl, stream, &own, y);
 }

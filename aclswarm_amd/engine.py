@@ -1772,7 +1772,7 @@ class FleetTrial(_LossyLinks):
     records = Trial.records
 
 
-class FleetEstTrial(FleetTrial):
+class FleetEstTrial(FleetTrial, _TableLinks):
     """Monte-Carlo trials on each vehicle's own estimates
     (acl_fleet_est_trial_init / acl_fleet_est_trial_batch, added within ABI
     11): FleetTrial in which no vehicle reads the shared snapshot q. Every
@@ -1792,22 +1792,50 @@ class FleetEstTrial(FleetTrial):
     records, all set by acl_fleet_est_trial_init. diag=True also records, per
     step, how wrong the tables are against the true q (the err2 maxima of the
     header, m^2). Raises ValueError on a malformed argument before anything
-    runs."""
+    runs.
+
+    table_latency / max_table_latency / feed_loss as _TableLinks takes them,
+    or encounters=True: the trials run acl_fleet_delay_est_trial_init /
+    acl_fleet_delay_est_trial_batch instead -- tables arrive whole gossip
+    rounds late and a vehicle's own feed may drop out (n_missed counts the
+    skipped senses; the object owns the publication log loc_ws). With none of
+    the four the object calls the entries above, as before. encounters=True
+    (alone: every table link at 0) also keeps the encounter record: per step,
+    from the true q and the tables the step's control reads, the smallest true
+    planar separation and its pair, the pairs inside r_keep_out, and per
+    running controller the vehicles truly within d_avoid_thresh that its table
+    does not show there (blind) and those its table shows there that are not
+    (ghost). enc [B] holds the acl_fleet_encounter_status_t records, enc_blind /
+    enc_ghost [B][n] i32 the counts per vehicle; encounters() returns them."""
 
     LOC_KEYS = ("loc_stamp", "loc_est", "loc_round", "loc_n_lost", "loc_Pt", "xst")
+    enc = enc_blind = enc_ghost = None
 
     def __init__(self, table, fseq, q, vel, params=None, cntrl=None, safety=None, queue_cap=None,
                  max_iter=0, ticks_per_step=10, latency=None, max_latency=None, loss=None,
-                 loss_seed=None, track_every=2, diag=False):
+                 loss_seed=None, track_every=2, diag=False, table_latency=None,
+                 max_table_latency=None, feed_loss=None, encounters=False):
         self._check_track_every("FleetEstTrial", track_every)
         if loss is None and loss_seed is not None:
             raise ValueError("FleetEstTrial: loss_seed is given without loss")
+        if not isinstance(encounters, (bool, np.bool_)):
+            raise ValueError(f"FleetEstTrial: encounters = {encounters!r} must be a bool")
         self.track_every, self.diag = int(track_every), bool(diag)
+        self.record_encounters = bool(encounters)
+        if encounters and table_latency is None and max_table_latency is None \
+                and feed_loss is None:
+            table_latency = 0
         super().__init__(table, fseq, q, vel, params=params, cntrl=cntrl, safety=safety,
                          queue_cap=queue_cap, max_iter=max_iter, ticks_per_step=ticks_per_step,
                          latency=1 if latency is None else latency, max_latency=max_latency,
                          loss=0 if loss is None else loss, loss_seed=loss_seed)
         B, n, dev = self.B, self.n, self.device
+        self._table_setup("FleetEstTrial", table_latency, max_table_latency, feed_loss, B, n, dev)
+        if self.record_encounters:
+            self.enc = torch.empty((B, L.FLEET_ENCOUNTER_STATUS_DTYPE.itemsize),
+                                   dtype=torch.uint8, device=dev)
+            self.enc_blind = torch.empty((B, n), dtype=torch.int32, device=dev)
+            self.enc_ghost = torch.empty((B, n), dtype=torch.int32, device=dev)
         self.loc_stamp = torch.empty((B, n, n), dtype=torch.int32, device=dev)
         self.loc_est = torch.empty((B, n, n, 3), dtype=torch.float64, device=dev)
         self.loc_round = torch.empty((B,), dtype=torch.int32, device=dev)
@@ -1816,11 +1844,17 @@ class FleetEstTrial(FleetTrial):
         self.xst = torch.empty((B, L.FLEET_EST_EPISODE_STATUS_DTYPE.itemsize), dtype=torch.uint8,
                                device=dev)
         # (the base class ran the delay entry's init; this one repeats it and
-        # sets the own-estimate arrays and the workspace tail)
-        x = self._est_args(0)
+        # sets the own-estimate arrays and the workspace tail; with table
+        # links also the empty log, n_missed and the encounter record)
         stream = ct.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        L.check(L.lib().acl_fleet_est_trial_init(ct.byref(x), n, stream),
-                "acl_fleet_est_trial_init")
+        if self.table_latency is not None:
+            y = self._delay_est_args(0)
+            L.check(L.lib().acl_fleet_delay_est_trial_init(ct.byref(y), n, stream),
+                    "acl_fleet_delay_est_trial_init")
+        else:
+            x = self._est_args(0)
+            L.check(L.lib().acl_fleet_est_trial_init(ct.byref(x), n, stream),
+                    "acl_fleet_est_trial_init")
 
     @staticmethod
     def _check_track_every(what, track_every):
@@ -1845,13 +1879,32 @@ class FleetEstTrial(FleetTrial):
             x.err2_hist = err2.data_ptr()
         return x
 
-    def run(self, steps, history=False, stream=None, own_estimates=True):
+    def _delay_est_args(self, steps, hist=None):
+        """FleetDelayEstTrialArgs around _est_args's FleetEstTrialArgs."""
+        y = L.FleetDelayEstTrialArgs()
+        enc = hist.pop("enc", None) if hist is not None else None
+        y.est = self._est_args(steps, hist)
+        self._table_args("FleetEstTrial.run", y, "loc_n_missed", "loc_workspace")
+        if self.record_encounters:
+            for k in ("enc", "enc_blind", "enc_ghost"):
+                setattr(y, k, getattr(self, k).data_ptr())
+            if enc is not None:
+                hist["enc"] = enc
+                y.enc_hist = enc.data_ptr()
+        return y
+
+    def run(self, steps, history=False, stream=None, own_estimates=True, table_links=True):
         """FleetTrial.run; with history=True and diag set the dict also holds
         "err2" [steps][B][3] f64 (own, nbr, all; rows of BAD_INPUT swarms and
         finished trials stay 0). own_estimates=False flies the steps on
         acl_fleet_lossy_trial_batch instead (the shared snapshot q; the
         trackers and loc_Pt stand still): a trial may move between the two
-        entries from run to run."""
+        entries from run to run. An object with table links or encounters
+        flies acl_fleet_delay_est_trial_batch; with history=True and
+        encounters the dict also holds "enc" [steps][B][24] u8, the
+        acl_fleet_encounter_step_t records (_lib.FLEET_ENCOUNTER_STEP_DTYPE).
+        table_links=False flies these steps on acl_fleet_est_trial_batch
+        instead (tables within the round, no record; the log stands still)."""
         if not own_estimates:
             return super().run(steps, history=history, stream=stream)
         steps = int(steps)
@@ -1865,12 +1918,23 @@ class FleetEstTrial(FleetTrial):
         hist = self._histories(steps) if history else None
         if history and self.diag:
             hist["err2"] = torch.zeros((steps, self.B, 3), dtype=torch.float64, device=dev)
-        x = self._est_args(steps, hist)
+        delayed = table_links and self.table_latency is not None
+        if history and delayed and self.record_encounters:
+            hist["enc"] = torch.zeros((steps, self.B, L.FLEET_ENCOUNTER_STEP_DTYPE.itemsize),
+                                      dtype=torch.uint8, device=dev)
         F = self.table.struct()
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
-        L.check(L.lib().acl_fleet_est_trial_batch(ct.byref(F), ct.byref(x), ct.c_void_p(stream)),
-                "acl_fleet_est_trial_batch")
+        if delayed:
+            y = self._delay_est_args(steps, hist)
+            L.check(L.lib().acl_fleet_delay_est_trial_batch(ct.byref(F), ct.byref(y),
+                                                            ct.c_void_p(stream)),
+                    "acl_fleet_delay_est_trial_batch")
+        else:
+            x = self._est_args(steps, hist)
+            L.check(L.lib().acl_fleet_est_trial_batch(ct.byref(F), ct.byref(x),
+                                                      ct.c_void_p(stream)),
+                    "acl_fleet_est_trial_batch")
         self.step += steps
         return hist
 
@@ -1882,7 +1946,22 @@ class FleetEstTrial(FleetTrial):
         st = super().fleet_status()
         st["estimates"] = np.ascontiguousarray(self.xst.cpu().numpy()).view(
             L.FLEET_EST_EPISODE_STATUS_DTYPE).reshape(-1)
+        if self.record_encounters:
+            st["encounters"] = self.encounters()["status"]
         return st
+
+    def encounters(self):
+        """The encounter record: {"status": the acl_fleet_encounter_status_t
+        records, structured numpy [B] (sep2_min in m^2, +inf before any pair;
+        step, i, j; n_breach, n_blind, n_ghost), "blind", "ghost": numpy
+        [B][n] i32, per vehicle}; synchronises. Raises ValueError on an object
+        made without encounters=True."""
+        if not self.record_encounters:
+            raise ValueError("FleetEstTrial.encounters: the object was made without "
+                             "encounters=True")
+        return {"status": np.ascontiguousarray(self.enc.cpu().numpy()).view(
+                    L.FLEET_ENCOUNTER_STATUS_DTYPE).reshape(-1),
+                "blind": self.enc_blind.cpu().numpy(), "ghost": self.enc_ghost.cpu().numpy()}
 
 
 def generate_formation_groups(seeds, n, fc, l, w, h, min_dist=2.0, max_candidates=0,

@@ -974,8 +974,8 @@ acl_status_t acl_fleet_localize_batch(const acl_formations_t* formations,
  *
  * Not modelled: latencies finer than a round; outages that depend on history
  * (bursts); n > 128. The closed loop on this entry is
- * acl_fleet_delay_est_episode_batch; the trials on own estimates still run
- * acl_fleet_localize_batch. */
+ * acl_fleet_delay_est_episode_batch, the trials on it are
+ * acl_fleet_delay_est_trial_batch. */
 typedef struct {
   acl_fleet_localize_args_t base;
   const uint8_t* tlat;       /* [B][n][n] receiver-major, rounds; diagonal ignored */
@@ -1580,8 +1580,8 @@ acl_status_t acl_fleet_est_episode_batch(const acl_formations_t* formations,
  * without loc_n_missed; with B > 0 and steps > 0: tlat NULL, loc_workspace NULL
  * or loc_workspace_bytes too small.
  * Not modelled: what acl_fleet_delay_localize_batch and
- * acl_fleet_est_episode_batch do not model; the trials on own estimates
- * (acl_fleet_est_trial_batch) still gossip within the round. */
+ * acl_fleet_est_episode_batch do not model (the trials on these links are
+ * acl_fleet_delay_est_trial_batch, below). */
 typedef struct {
   acl_fleet_est_episode_args_t est;
   const uint8_t* tlat;       /* [B][n][n] receiver-major, rounds; diagonal ignored */
@@ -2075,6 +2075,127 @@ acl_status_t acl_fleet_est_trial_init(const acl_fleet_est_trial_args_t* args, in
                                       void* stream);
 acl_status_t acl_fleet_est_trial_batch(const acl_formations_t* formations,
                                        const acl_fleet_est_trial_args_t* args, void* stream);
+
+/* ---- the trials on own estimates with tables on real links, and the encounter
+ * record (added within ABI 11) ----------------------------------------------
+ * acl_fleet_delay_est_trial_batch is acl_fleet_est_trial_batch with one
+ * sentence changed: the gossip round of step 2 is one round of
+ * acl_fleet_delay_localize_batch under tlat, max_tlat and feed_loss, with the
+ * same link.loss / link.seed. It runs under loc_Pt and the hand-off's formation
+ * (-1 for a finished or skipped trial), after the step's commit, and
+ * loc_round[b] is the publication round: the tag of the log slot, the word of
+ * the loss hash and of the feed hash. Skipped senses count in loc_n_missed.
+ * Everything else is acl_fleet_est_trial_batch's: loc_Pt is written by
+ * adoptions only, the commit touches neither the trackers nor the publication
+ * log, and a finished trial is handed over with formation -1 and left alone,
+ * its log included. Added symbols: ACL_ABI_VERSION stays 11 (no existing struct
+ * or call changed).
+ *
+ * What the trial shows and no episode does:
+ *  (a) a table published before a commit and due after it is delivered to
+ *      whoever subscribes to its sender IN THE DELIVERY ROUND: under the new
+ *      formation's adjacency and the receiver's unchanged loc_Pt. The first
+ *      auction of every new formation starts from those tables;
+ *  (b) with tlat all zero and feed_loss NULL this is acl_fleet_est_trial_batch
+ *      byte for byte, whatever loc_workspace holds;
+ *  (c) steps a then b equals a + b, with tables in flight across the call
+ *      boundary and across a commit;
+ *  (d) a swarm with an off-diagonal tlat entry above max_tlat gets
+ *      ACL_FLEET_BAD_INPUT at the call's first hand-off, for that swarm only:
+ *      it is skipped for the call like a swarm with a bad row, untouched in
+ *      every respect, its log, loc_n_missed and its encounter record included.
+ *
+ * The localization workspace (acl_fleet_delay_localize_workspace_bytes(n, B,
+ * max_tlat)) holds the publication log and is its own; the trial workspace is
+ * that of acl_fleet_est_trial_batch and its layout does not move, so a trial
+ * may move between acl_fleet_delay_trial_batch, acl_fleet_lossy_trial_batch,
+ * acl_fleet_est_trial_batch and this entry from call to call (a table published
+ * under another entry is not in the log: it is not delivered and not lost).
+ *
+ * The encounter record (enc != NULL; enc NULL: no record, nothing is launched
+ * for it). Per step, after the step's ticks and before its hand-off, from the
+ * true q[b] and the tables loc_est[b] that this step's control reads, for every
+ * swarm neither finished nor skipped. All distances are planar, as
+ * collisionAvoidance's are: s2(d) = d.x * d.x + d.y * d.y, one IEEE operation
+ * each.
+ *   true separation  the minimum of s2(q[j] - q[i]) over the unordered pairs
+ *                    i < j; among equal values the lowest (i, j)
+ *                    lexicographically. A NaN is never a minimum. With n == 1
+ *                    (or every pair NaN) the value is +inf and the pair is
+ *                    (0xFFFF, 0xFFFF);
+ *   breaches         the pairs i < j with s2 < r_keep_out * r_keep_out;
+ *   blind, ghost     for every vehicle v whose controller runs this step
+ *                    (ctl_on after this step's hand-off: ctl_on, or an adoption
+ *                    in this step's ticks) and every j != v, with
+ *                    cand(d) = !(sqrt(s2(d)) > d_avoid_thresh), the candidate
+ *                    test of collisionAvoidance (safety.cpp:412-420) as
+ *                    acl_fleet_est_control_batch applies it:
+ *                      cand_true = cand(q[j] - q[v])
+ *                      cand_est  = cand(loc_est[v][j] - loc_est[v][v])
+ *                    blind: cand_true && !cand_est -- a vehicle truly inside
+ *                    the avoidance range that v's avoidance does not see;
+ *                    ghost: !cand_true && cand_est -- v avoids something that
+ *                    is not there (a never-heard-of vehicle sits at the origin
+ *                    of v's table). A stopped controller counts nothing.
+ * enc[b] holds the smallest true separation of the flight with the step and the
+ * pair at which it occurred (replaced under strict <: the earliest step wins)
+ * and the totals; enc_blind / enc_ghost [B][n] hold the totals per vehicle v;
+ * enc_hist [steps][B] (or NULL) the step's own figures. All accumulate across
+ * calls. A finished or skipped trial writes none of them.
+ *
+ * acl_fleet_delay_est_trial_init is acl_fleet_est_trial_init on `est`, plus:
+ * loc_workspace zero-filled (an empty log), loc_n_missed zeroed (if given),
+ * and with enc: sep2_min +inf, step -1, pair 0xFFFF, every count 0.
+ *
+ * Argument errors, reported before any HIP call: those of
+ * acl_fleet_est_trial_batch (acl_fleet_est_trial_init) on `est`; max_tlat
+ * outside 0..7; feed_loss without loc_n_missed; enc without enc_blind or
+ * enc_ghost; with B > 0 (and, for the batch, steps > 0): tlat NULL,
+ * loc_workspace NULL or loc_workspace_bytes too small. Stream-ordered, never
+ * synchronises.
+ *
+ * Not modelled: what acl_fleet_delay_localize_batch and
+ * acl_fleet_est_trial_batch do not model; a delay between an adoption and the
+ * vehicle's own localization node hearing of it; 3-D separation (the record is
+ * planar because the reference's avoidance is); n > 128. */
+typedef struct {
+  double  sep2_min;  /* m^2; +inf: no pair yet */
+  int32_t step;      /* the global step of sep2_min; -1: none */
+  uint16_t i, j;     /* its pair, i < j; 0xFFFF: none */
+  int32_t n_breach;  /* pair-steps inside r_keep_out */
+  int32_t n_blind;   /* ordered pair-steps, above */
+  int32_t n_ghost;
+  int32_t reserved;
+} acl_fleet_encounter_status_t; /* 32 bytes */
+
+typedef struct {
+  double   sep2;     /* the step's minimum, +inf: none */
+  uint16_t i, j;     /* 0xFFFF: none */
+  uint16_t n_breach; /* <= 8 128 */
+  uint16_t n_blind;  /* <= 16 256 */
+  uint16_t n_ghost;
+  uint16_t pad[3];
+} acl_fleet_encounter_step_t; /* 24 bytes */
+
+typedef struct {
+  acl_fleet_est_trial_args_t est;
+  const uint8_t* tlat;       /* [B][n][n] receiver-major, rounds; diagonal ignored */
+  int32_t max_tlat;          /* 0..7 */
+  const uint16_t* feed_loss; /* [B][n] or NULL */
+  int32_t* loc_n_missed;     /* [B][n] in/out; required with feed_loss */
+  void* loc_workspace;       /* acl_fleet_delay_localize_workspace_bytes */
+  size_t loc_workspace_bytes;
+  acl_fleet_encounter_status_t* enc;    /* [B] in/out, or NULL: no record */
+  int32_t* enc_blind;                   /* [B][n] in/out; required with enc */
+  int32_t* enc_ghost;                   /* [B][n] in/out; required with enc */
+  acl_fleet_encounter_step_t* enc_hist; /* [steps][B] or NULL */
+} acl_fleet_delay_est_trial_args_t;
+
+acl_status_t acl_fleet_delay_est_trial_init(const acl_fleet_delay_est_trial_args_t* args,
+                                            int32_t n, void* stream);
+acl_status_t acl_fleet_delay_est_trial_batch(const acl_formations_t* formations,
+                                             const acl_fleet_delay_est_trial_args_t* args,
+                                             void* stream);
 
 /* ---- random formation groups on the device -----------
  * Replaces aclswarm_sim/nodes/generate_random_formation.py:59-80
